@@ -17,7 +17,7 @@ independent: rank k owns the global replicas [k*B, (k+1)*B) (request stream = (s
 run simulates exactly the replicas of the unsharded one); the only collective is the RCCL all-reduce of the statistics
 vector after the timed region.  `--scaling weak`: B = --batch per GPU; `--scaling strong`: --batch is the GLOBAL batch.
 Inputs are generated on device (include/ongym_traffic.h) and all state is HBM-resident when the timed region starts.
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  `--dump-outputs DIR` then also writes what the timed path computed (see dump_outputs).
 """
 import argparse
 import json
@@ -51,6 +51,10 @@ REFERENCE_MEASURED = {
     "nobeleu768": {"steps_per_s_1core_nsfnet768_load600": 282.0, "steps_per_s_8procs_nsfnet768_load600": 1636.0},
 }
 MIN_FILL_ENV_STEPS = 999     # one whole episode (warm-up 1 episode)
+DUMP_MAX_BYTES = 64_000_000  # --dump-outputs: all arrays together
+DUMP_RECORD_BYTES = 32 << 20 # --dump-outputs --record: the share of the step records
+DUMP_REPLICAS = 4096         # --dump-outputs: size of the fixed replica sample
+DUMP_GRIDS = 8               # --dump-outputs: spectrum grids of the first replicas of the sample
 
 
 def jocn_modulations():
@@ -164,6 +168,61 @@ def cpu_baseline(tables, wl, workload, policy=0, seconds_target=12.0):
     return out
 
 
+def dump_plan(B, spl, n_links, n_slots, record):
+    """What --dump-outputs will write for B replicas, known before anything runs: (replica sample, replicas whose step
+    records are written or None, bytes of all arrays)."""
+    from optical_networking_gym import _native as nat
+    sample = np.sort(np.random.default_rng(0).choice(B, size=min(B, DUMP_REPLICAS), replace=False))
+    per_replica = 1 + sum(int(np.prod(nat.STATS_DTYPE.fields[f][0].shape)) for f in nat.STATS_DTYPE.names if not f.endswith("_"))
+    total = len(sample) * per_replica * 8 + min(len(sample), DUMP_GRIDS) * n_links * n_slots * 8
+    cols = None
+    if record:
+        per_record_replica = (spl * len(nat.STEP_DTYPE.names) + 1) * 8
+        q = max(1, min(len(sample), DUMP_RECORD_BYTES // per_record_replica))
+        cols = sample[np.linspace(0, len(sample) - 1, q).astype(np.int64)]
+        total += q * per_record_replica
+    return sample, cols, total
+
+
+def dump_outputs(out_dir, env, stats, base, spl, rec_buf=None):
+    """--dump-outputs DIR: what the timed path computed, read after its last step, as float64 .npy files, so that two builds
+    run with the same arguments (the requests are drawn on device from --seed: identical inputs) compare output for output.
+    A fixed, seeded sample of this rank's replicas (all of them when there are at most DUMP_REPLICAS) stands for the batch:
+      replica_index.npy   [R]         global replica index of each sampled replica
+      stats_<field>.npy   [R] / [R,8] per-replica statistics (ongym_stats): `stats`, env.stats() after the last step
+      grid.npy            [G, E, S]   spectrum grid (env.grid) of the first DUMP_GRIDS sampled replicas
+      record_<field>.npy  [spl, Q]    --record only: the step records of the last timed launch (what the kernel wrote to the
+                                      caller's device buffer), Q replicas spread evenly over the sample
+    main() checks beforehand that dump_plan stays within DUMP_MAX_BYTES.  A DIR that this call creates also gets a
+    .gitignore of "*", so a dump inside the work tree stays out of git."""
+    from optical_networking_gym import _native as nat
+    B = env.batch_size
+    c = env.holder.struct
+    sample, cols, _ = dump_plan(B, spl, c.n_links, c.n_slots, rec_buf is not None)
+    arrays = {"replica_index": (base + sample).astype(np.float64)}
+    st = stats[sample]
+    for f in nat.STATS_DTYPE.names:
+        if not f.endswith("_"):                                  # reserved0_: padding of the C struct
+            arrays[f"stats_{f}"] = st[f].astype(np.float64)
+    arrays["grid"] = np.stack([env.grid(int(r)) for r in sample[:DUMP_GRIDS]]).astype(np.float64)
+    if rec_buf is not None:
+        import torch
+        names, q = nat.STEP_DTYPE.names, len(cols)
+        raw = rec_buf.view(spl, B, nat.STEP_DTYPE.itemsize).index_select(1, torch.as_tensor(cols, device=rec_buf.device))
+        rec = raw.cpu().numpy().reshape(-1).view(nat.STEP_DTYPE).reshape(spl, q)
+        arrays["record_replica_index"] = (base + cols).astype(np.float64)
+        for f in names:
+            arrays[f"record_{f}"] = rec[f].astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if not os.path.isdir(out_dir):
+        os.makedirs(out_dir)
+        with open(os.path.join(out_dir, ".gitignore"), "w") as f:
+            f.write("# written by bench.py --dump-outputs\n*\n")
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return {"dir": out_dir, "files": len(arrays), "bytes": int(total), "replicas": int(len(sample))}
+
+
 def busy_frac(pmc, key, occ):
     cyc, wave = pmc.get(key), pmc.get("wave_cycles_per_env_step")
     if cyc is None or not wave or not occ.get("blocks_per_cu"):
@@ -203,6 +262,8 @@ def main():
                          "10 lowest fragmentation have lean kernels; the others run the generic kernel")
     ap.add_argument("--record", action="store_true", help="write the per-step record (the reference's `info`) for every step")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed to DIR/<name>.npy (rank 0's replicas, see dump_outputs)")
     args = ap.parse_args()
     if args.steps <= 0 or args.warmup < 0 or args.steps_per_launch <= 0:
         raise SystemExit("--steps and --steps-per-launch must be positive, --warmup non-negative")
@@ -240,13 +301,18 @@ def main():
     global_batch = args.batch * world if args.scaling == "weak" else args.batch
     base, local_batch = shard_bounds(global_batch, rank, world)      # this rank's slice of the global replicas
     tables = build_tables(wl["topology"])
+    if args.dump_outputs:       # every rank, before anything runs: rank 0 (replicas [0, B0)) is the one that writes
+        dump_bytes = dump_plan(shard_bounds(global_batch, 0, world)[1], spl, tables.n_links, wl["S"], args.record)[2]
+        if dump_bytes > DUMP_MAX_BYTES:
+            raise SystemExit(f"--dump-outputs: {dump_bytes} bytes exceed the {DUMP_MAX_BYTES}-byte limit "
+                             f"(--steps-per-launch {spl} with --record)")
     env = BatchedQRMSAEnv(tables=tables, modulations=jocn_modulations(), batch_size=local_batch, device=device,
                           io_device=bool(args.record), num_spectrum_resources=wl["S"], capacity=wl["capacity"], episode_length=1000,
                           auto_reset=True, load=wl["load"], bit_rate_selection="discrete", bit_rates=wl["bit_rates"])
     env.seed(args.seed, replica_base=base)
     env.reset()
 
-    rec_ptr = None
+    rec_buf = rec_ptr = None
     if args.record:     # the per-step records (the reference's `info`, qrmsa.pyx:996-1060) of one launch, kept in HBM
         from optical_networking_gym import _native as nat
         rec_buf = torch.empty(spl * local_batch * nat.STEP_DTYPE.itemsize, dtype=torch.uint8, device=f"cuda:{device}")
@@ -277,6 +343,7 @@ def main():
     fence()
     dt = time.perf_counter() - t0
     s1 = env.stats()
+    dumped = dump_outputs(args.dump_outputs, env, s1, base, spl, rec_buf) if (args.dump_outputs and rank == 0) else None
 
     fields = ("total_steps", "total_accepted", "total_gn_evals", "total_interferer_terms", "total_paths_tried",
               "total_path_hops", "total_active_sum")
@@ -371,6 +438,8 @@ def main():
                                 "backend": (dist.get_backend() if dist else None),
                                 "per_rank_value": [r[0] for r in per_rank], "per_rank_avg_launch_ms": [r[1] for r in per_rank],
                                 "per_rank_batch": [int(r[2]) for r in per_rank]}
+        if dumped:
+            out["dump_outputs"] = dumped
         if rehearse:
             out["rehearsal"] = "ranks share GPUs, gloo reduction: plumbing check only, not a measurement"
         # the timed state must be the loaded network: by Little's law the carried load (offered x accepted fraction) is the mean

@@ -33,6 +33,13 @@ def golden_tables(name: str) -> StaticTables:
     return _tables_cache[name]
 
 
+def record_bytes(rec: np.ndarray) -> bytes:
+    """The bytes of every named field of a structured array, field after field, without the alignment padding between
+    fields (STEP_DTYPE: 4 bytes after `active`).  The kernels never set the padding, so its bytes are unspecified (in practice
+    whatever the output buffer held before): bit-for-bit comparisons of step records go through this."""
+    return b"".join(np.ascontiguousarray(rec[f]).tobytes() for f in rec.dtype.names)
+
+
 def load_traj(tag: str):
     meta = json.load(open(os.path.join(GOLDEN, tag + ".json")))
     data = np.load(os.path.join(GOLDEN, tag + ".npz"))

@@ -4,7 +4,7 @@ GSNR within GSNR_RTOL (the north star allows 1e-5 relative; the fp64 span-hoiste
 import numpy as np
 import pytest
 
-from common import ALL_TRAJ, golden_tables, holder_for, jocn_modulations, load_traj, traj_requests
+from common import ALL_TRAJ, golden_tables, holder_for, jocn_modulations, load_traj, record_bytes, traj_requests
 from optical_networking_gym import _native as nat
 from optical_networking_gym.envs.batched import BatchedQRMSAEnv, OngymError
 from oracle_lib import OracleEnv
@@ -451,7 +451,8 @@ def test_random_request_traces_vs_oracle(case, on_table):
 def test_sharded_batch_equals_unsharded_bit_exact():
     """A batch split over two environments with replica bases 0 and B/2 (what two ranks of bench.py / a sharded sweep
     own, `shard_bounds`) reproduces the single environment of B replicas bit for bit: per-replica statistics, grids and
-    step records.  SURVEY §4 item (4): sharded == unsharded; graph_load.py:361-363 fans out the same way."""
+    step records.  SURVEY §4 item (4): sharded == unsharded; graph_load.py:361-363 fans out the same way.  Step records are compared field by field
+    (`record_bytes`): their alignment padding is never written and is left out on purpose, not a raw tobytes()."""
     from optical_networking_gym._dist import shard_bounds
     tb = golden_tables("nsfnet")
     B, steps = 512, 1100
@@ -468,7 +469,7 @@ def test_sharded_batch_equals_unsharded_bit_exact():
         parts.append(e)
     st_parts = np.concatenate([e.stats() for e in parts])
     assert st_parts.tobytes() == st_whole.tobytes()
-    assert np.concatenate(recs, axis=1).tobytes() == rec_whole.tobytes()
+    assert record_bytes(np.concatenate(recs, axis=1)) == record_bytes(rec_whole)
     for r in (0, B // 2 - 1, B // 2, B - 1):
         e, lr = (parts[0], r) if r < B // 2 else (parts[1], r - B // 2)
         np.testing.assert_array_equal(e.grid(lr), whole.grid(r))
@@ -483,7 +484,8 @@ def test_narrow_and_wide_lean_builds_agree_bit_exact(pid, monkeypatch):
     configuration is <= 32 (one-step run-AND shifts, two-word marks, no wide-release path) and is what NSFNET-320 runs; the
     wide one (ONGYM_FORCE_WIDE=1 selects it for any configuration) is the general code.  Same arithmetic in the same
     order: step records, statistics and grids must be identical bit for bit.  (The wide build is held to the oracle with
-    slot counts up to 80 by the *_wide_services_* tests, the narrow one by every NSFNET / COST239 / nobel-eu test.)"""
+    slot counts up to 80 by the *_wide_services_* tests, the narrow one by every NSFNET / COST239 / nobel-eu test.)  Step records are compared field by field
+    (`record_bytes`): their alignment padding is never written and is left out on purpose, not a raw tobytes()."""
     tb = golden_tables("nsfnet")
     B, steps = 256, 1100 if pid in (nat.POLICY_FIRST_FIT, nat.POLICY_LOAD_BALANCING) else 400
     kw = dict(tables=tb, modulations=jocn_modulations(), num_spectrum_resources=320, capacity=448, load=320,
@@ -495,7 +497,7 @@ def test_narrow_and_wide_lean_builds_agree_bit_exact(pid, monkeypatch):
         e = BatchedQRMSAEnv(**kw); e.seed(11); e.reset()
         assert e.occupancy(pid)["lean_kernel"]
         rec = e.step_policy(steps, policy=pid)
-        outs.append((rec.tobytes(), e.stats().tobytes(), [e.grid(r).tobytes() for r in (0, 17, B - 1)]))
+        outs.append((record_bytes(rec), e.stats().tobytes(), [e.grid(r).tobytes() for r in (0, 17, B - 1)]))
     assert outs[0][0] == outs[1][0], "step records differ between the narrow and the wide build"
     assert outs[0][1] == outs[1][1], "statistics differ between the narrow and the wide build"
     assert outs[0][2] == outs[1][2], "grids differ between the narrow and the wide build"
@@ -531,7 +533,8 @@ def test_lean_launch_longer_than_the_32_bit_sum_allows_is_split_on_the_host():
     """The lean kernels add up the running services of their steps in 32 bits; `fast_launch` (csrc/ongym_fast.hip) therefore
     splits a launch so that steps x capacity stays below 2^32.  With capacity 8192 the limit is 524 287 steps: one call of
     524 287 + 60 steps (two launches, the step records of the second one written behind the first one's) must equal the same
-    steps made in two calls, bit for bit."""
+    steps made in two calls, bit for bit.  Step records are compared field by field
+    (`record_bytes`): their alignment padding is never written and is left out on purpose, not a raw tobytes()."""
     tb = golden_tables("nsfnet")
     cap = 8192
     chunk = 0xFFFFFFFF // cap
@@ -543,7 +546,7 @@ def test_lean_launch_longer_than_the_32_bit_sum_allows_is_split_on_the_host():
     b = BatchedQRMSAEnv(**kw); b.seed(3); b.reset()
     b.step_policy(chunk, record=False)
     rec_b = b.step_policy(60)
-    assert rec_a[chunk:].tobytes() == rec_b.tobytes()
+    assert record_bytes(rec_a[chunk:]) == record_bytes(rec_b)
     assert a.stats().tobytes() == b.stats().tobytes()
     st = a.stats()
     assert int(st["total_steps"][0]) == chunk + 60 and int(st["services_processed"][0]) >= chunk + 60

@@ -20,7 +20,7 @@ from optical_networking_gym.utils import rle
 from oracle_lib import OracleEnv
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REFERENCE_TOPOLOGIES = "/root/reference/examples/topologies"
+SNDLIB_TOPOLOGIES = GOLDEN          # the reference's SNDlib topology files (examples/topologies), stored as fixtures
 
 
 def tables_equal(a: StaticTables, b: StaticTables):
@@ -40,10 +40,9 @@ def test_topology_compiler_matches_reference_tables(fname, gold):
     tables_equal(StaticTables.from_topology(topo), golden_tables(gold))
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE_TOPOLOGIES), reason="reference data files only exist in the build container")
 @pytest.mark.parametrize("fname,gold", [("nobel-eu.xml", "nobel-eu"), ("germany50.xml", "germany50")])
 def test_sndlib_reader_matches_reference_tables(fname, gold):
-    topo = get_topology(os.path.join(REFERENCE_TOPOLOGIES, fname), None, jocn_modulations(), 80, 0.2, 4.5, 5)
+    topo = get_topology(os.path.join(SNDLIB_TOPOLOGIES, fname), None, jocn_modulations(), 80, 0.2, 4.5, 5)
     tables_equal(StaticTables.from_topology(topo), golden_tables(gold))
 
 
