@@ -285,6 +285,37 @@ int ongym_observe(ongym_env *env, float *obs, uint8_t *mask);
  * mask / actions: host buffers, or device buffers with cfg.io_device (then nothing synchronises). */
 int ongym_sample_actions(ongym_env *env, const uint8_t *mask, uint64_t seed, uint64_t draw_index, int32_t *actions);
 
+/* Masked categorical action head: the action distribution of the reference's masked PPO training
+ * (examples/ONDM_2025/train_multi_masked_ppo.py: sb3-contrib MaskablePPO, whose MaskableCategorical is a Categorical over
+ * logits with the masked entries filled with -1e8) over the env's action mask, evaluated on device in ONE pass per row.
+ * Semantics are the exact masked distribution (what the -1e8 fill approximates): masked entries do not exist, whatever their
+ * logit holds (NaN and +-inf included); p = softmax over the valid entries, entropy = -sum_valid p log p.
+ *   logits  [batch][n_actions] of type `dtype` (ONGYM_DTYPE_*), 16-byte aligned base; n_actions = k_paths*Mc*n_slots + 1
+ *   mask    uint8 [batch][n_actions] as the observation call writes it (nonzero = valid), 8-byte aligned base
+ *   mode    ONGYM_HEAD_SAMPLE: draw from the masked softmax (MaskableCategorical.sample): Gumbel-max, per-entry uniforms of the
+ *             counter-based generator of ongym_traffic.h, one stream per (seed, global replica = replica_base + r,
+ *             draw_index) countered by entry, in a domain of its own (not the uniform sampler's stream);
+ *           ONGYM_HEAD_ARGMAX: the first valid entry with the largest logit (MaskableCategorical.mode(), deterministic=True);
+ *           ONGYM_HEAD_EVALUATE: log-prob and entropy of the GIVEN actions (MaskablePPO's evaluate_actions); actions are read.
+ * Outputs per row: actions (written in the first two modes), log_prob, entropy, lse (the masked log-sum-exp, kept for the
+ * backward call), mask_bits uint32 [batch][ceil(n_actions/32)] (bit j of row r = mask[r][j] != 0); every output but actions
+ * may be NULL.  Rows where only the reject entry is valid give (reject, 0, 0); rows with no valid entry (a caller error) give
+ * the reject action and NaN log_prob / entropy / lse; in evaluate mode an action outside the mask gets log_prob = -inf.
+ * Device pointers only: both calls fail with ONGYM_E_ARG unless cfg.io_device = 1.  Launched on the env's current stream
+ * (ongym_set_stream), nothing synchronises. */
+enum { ONGYM_DTYPE_F32 = 0, ONGYM_DTYPE_BF16 = 1 };
+enum { ONGYM_HEAD_SAMPLE = 0, ONGYM_HEAD_ARGMAX = 1, ONGYM_HEAD_EVALUATE = 2 };
+int ongym_masked_categorical(ongym_env *env, const void *logits, int32_t dtype, const uint8_t *mask, int32_t mode,
+                             uint64_t seed, uint64_t draw_index, int32_t *actions, float *log_prob, float *entropy,
+                             float *lse, uint32_t *mask_bits);
+/* Gradient of  sum_r g_lp[r] log_prob[r] + g_H[r] entropy[r]  with respect to the logits of the forward call above, from the
+ * saved mask bits, actions, lse and entropy (not the caller's mask, which the next observation overwrites):
+ * grad_logits[r][j] = valid ? g_lp (delta_{j,a} - p_j) - g_H p_j (log p_j + H) : 0, written in the logits' dtype.  g_lp / g_H
+ * (float [batch]) may be NULL (zero).  Same pointer, alignment and stream rules. */
+int ongym_masked_categorical_backward(ongym_env *env, const void *logits, int32_t dtype, const uint32_t *mask_bits,
+                                      const int32_t *actions, const float *lse, const float *entropy,
+                                      const float *grad_log_prob, const float *grad_entropy, void *grad_logits);
+
 /* Plugin-API queries on one replica (host buffers always): */
 /* QRMSAEnv.get_available_slots(path) (qrmsa.pyx:1482-1512): out[n_slots], 1 = free on every link of the path */
 int ongym_query_available(ongym_env *env, int32_t replica, int32_t path_id, int32_t *out);

@@ -18,6 +18,7 @@
 #include "ongym_host.hpp"
 #include "ongym_fast.hpp"      // fast_lds_bytes, PathRec (the kernels themselves: ongym_fast.hip)
 #include "ongym_scored.hpp"
+#include "ongym_policy_head.hpp"   // masked categorical action head (ongym_masked_categorical)
 
 using namespace ongym;
 
@@ -1289,6 +1290,67 @@ int ongym_sample_actions(ongym_env *env, const uint8_t *mask, uint64_t seed, uin
         HIP_TRY(env, hipMemcpyAsync(actions, d_act, B * 4, hipMemcpyDeviceToHost, env->stream));
         HIP_TRY(env, hipStreamSynchronize(env->stream));
     }
+    return ONGYM_OK;
+}
+
+// Masked categorical action head (csrc/ongym_policy_head.hpp): one wavefront per row, kHeadWaves rows per workgroup.
+static int head_check(ongym_env *env, const void *logits, int32_t dtype, const void *mask_or_bits, size_t mask_align) {
+    if (!env->cfg.io_device) return fail_arg(env, "the masked categorical head takes device buffers: needs cfg.io_device = 1");
+    if (!logits || !mask_or_bits) return fail_arg(env, "null logits / mask");
+    if (dtype != ONGYM_DTYPE_F32 && dtype != ONGYM_DTYPE_BF16) return fail_arg(env, "dtype must be ONGYM_DTYPE_F32 or ONGYM_DTYPE_BF16");
+    if ((uintptr_t)logits % 16) return fail_arg(env, "logits must be 16-byte aligned");
+    if ((uintptr_t)mask_or_bits % mask_align) return fail_arg(env, "mask must be 8-byte aligned");
+    return ONGYM_OK;
+}
+
+int ongym_masked_categorical(ongym_env *env, const void *logits, int32_t dtype, const uint8_t *mask, int32_t mode,
+                             uint64_t seed, uint64_t draw_index, int32_t *actions, float *log_prob, float *entropy,
+                             float *lse, uint32_t *mask_bits) {
+    if (!env) return ONGYM_E_ARG;
+    { int rc = head_check(env, logits, dtype, mask, 8); if (rc) return rc; }
+    if (!actions) return fail_arg(env, "null actions");
+    if (mode < ONGYM_HEAD_SAMPLE || mode > ONGYM_HEAD_EVALUATE) return fail_arg(env, "unknown head mode");
+    HIP_TRY(env, hipSetDevice(env->cfg.device));
+    const Params &P = env->P;
+    const int nact = P.k_paths * P.n_mods_consider * P.n_slots + 1, B = P.batch;
+    const size_t lds = (size_t)kHeadWaves * ((nact + 31) / 32) * 4;
+    if (lds > 64 * 1024) return fail_arg(env, "n_actions too large for the masked categorical head", ONGYM_E_LIMIT);
+    const dim3 grid((B + kHeadWaves - 1) / kHeadWaves), block(64 * kHeadWaves);
+    const size_t shm = mask_bits ? lds : 0;
+#define ONGYM_HEAD_FWD(DT, MODE)                                                                                           \
+    hipLaunchKernelGGL((k_head_fwd<DT, MODE>), grid, block, shm, env->stream,                                              \
+                       static_cast<const HeadElem<DT>::T *>(logits), mask, B, nact, seed, env->replica_base, draw_index,  \
+                       actions, log_prob, entropy, lse, mask_bits)
+#define ONGYM_HEAD_FWD_MODES(DT)                                                                                           \
+    if (mode == ONGYM_HEAD_SAMPLE) ONGYM_HEAD_FWD(DT, ONGYM_HEAD_SAMPLE);                                                  \
+    else if (mode == ONGYM_HEAD_ARGMAX) ONGYM_HEAD_FWD(DT, ONGYM_HEAD_ARGMAX);                                             \
+    else ONGYM_HEAD_FWD(DT, ONGYM_HEAD_EVALUATE)
+    if (dtype == ONGYM_DTYPE_F32) { ONGYM_HEAD_FWD_MODES(ONGYM_DTYPE_F32); }
+    else { ONGYM_HEAD_FWD_MODES(ONGYM_DTYPE_BF16); }
+#undef ONGYM_HEAD_FWD_MODES
+#undef ONGYM_HEAD_FWD
+    HIP_TRY(env, hipGetLastError());
+    return ONGYM_OK;
+}
+
+int ongym_masked_categorical_backward(ongym_env *env, const void *logits, int32_t dtype, const uint32_t *mask_bits,
+                                      const int32_t *actions, const float *lse, const float *entropy,
+                                      const float *grad_log_prob, const float *grad_entropy, void *grad_logits) {
+    if (!env) return ONGYM_E_ARG;
+    { int rc = head_check(env, logits, dtype, mask_bits, 4); if (rc) return rc; }
+    if (!actions || !lse || !entropy || !grad_logits) return fail_arg(env, "null actions / lse / entropy / grad_logits");
+    if ((uintptr_t)grad_logits % 16) return fail_arg(env, "grad_logits must be 16-byte aligned");
+    HIP_TRY(env, hipSetDevice(env->cfg.device));
+    const Params &P = env->P;
+    const int nact = P.k_paths * P.n_mods_consider * P.n_slots + 1, B = P.batch;
+    const dim3 grid((B + kHeadWaves - 1) / kHeadWaves), block(64 * kHeadWaves);
+    if (dtype == ONGYM_DTYPE_F32)
+        hipLaunchKernelGGL((k_head_bwd<ONGYM_DTYPE_F32>), grid, block, 0, env->stream, static_cast<const float *>(logits),
+                           mask_bits, B, nact, actions, lse, entropy, grad_log_prob, grad_entropy, static_cast<float *>(grad_logits));
+    else
+        hipLaunchKernelGGL((k_head_bwd<ONGYM_DTYPE_BF16>), grid, block, 0, env->stream, static_cast<const uint16_t *>(logits),
+                           mask_bits, B, nact, actions, lse, entropy, grad_log_prob, grad_entropy, static_cast<uint16_t *>(grad_logits));
+    HIP_TRY(env, hipGetLastError());
     return ONGYM_OK;
 }
 

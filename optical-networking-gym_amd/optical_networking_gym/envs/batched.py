@@ -55,6 +55,7 @@ class BatchedQRMSAEnv:
             raise OngymError(f"ongym_create failed ({rc}): {self.lib.ongym_last_error(None).decode()}")
         self._h = h
         self._trace = None
+        self.stream_handle = None       # the caller's stream given to set_stream (None: the environment's own)
 
     # ------------------------------------------------------------------------------------------------------------
     def close(self):
@@ -259,6 +260,7 @@ class BatchedQRMSAEnv:
             self._check(self.lib.ongym_set_stream(self._h, None, 1), "ongym_set_stream")
         else:       # 0 is HIP's default (null) stream: torch's default current stream
             self._check(self.lib.ongym_set_stream(self._h, C.c_void_p(int(stream_handle)), 0), "ongym_set_stream")
+        self.stream_handle = None if stream_handle is None else int(stream_handle)   # None: the environment's own stream
 
     def sync(self):
         self._check(self.lib.ongym_sync(self._h), "ongym_sync")

@@ -6,7 +6,8 @@ observation + action mask -> masked policy in PyTorch-ROCm -> step(actions), eve
     python tools/bench_rl.py [--gpus N] [--batch B] [--steps K] [--learner [--horizon H]]
 
 Default: a masked random policy (env-side cost only).  `--learner`: a masked actor-critic MLP (368 -> 512 -> 512 -> 9601
-logits + value head, bf16 autocast) sampled every step and updated with Adam on n-step returns every `--horizon` steps —
+logits + value head, bf16 autocast) sampled every step through the library's masked categorical head
+(optical_networking_gym.rl.masked_categorical on the bf16 logits) and updated with Adam on n-step returns every `--horizon` steps —
 the data flow of the reference's MaskablePPO scripts (examples/ONDM_2025/train_multi_masked_ppo.py:410-458: 14
 SubprocVecEnv workers feeding one learner; no PPO library is installed in this image).  The env writes into / reads from
 torch device tensors (`io_device=1`, torch.Tensor.data_ptr()); nothing crosses PCIe inside the loop.
@@ -63,6 +64,7 @@ def main():
     from optical_networking_gym._dist import (allreduce_mean_gradients, gather_per_rank, init_process_group,
                                               reduce_run_statistics, shard_bounds)
     from optical_networking_gym.envs.batched import BatchedQRMSAEnv
+    from optical_networking_gym.rl import masked_categorical
     rehearse = os.environ.get("ONGYM_BENCH_REHEARSE") == "1"       # ranks share the GPUs, gloo: plumbing check only
     device = local_rank % torch.cuda.device_count() if rehearse else local_rank
     torch.cuda.set_device(device)
@@ -150,13 +152,13 @@ def main():
             env_observe()
             with torch.autocast("cuda", dtype=torch.bfloat16):
                 h = body(obs)
-                logits, v = pi_head(h).float(), v_head(h).float().squeeze(1)
-            logits = logits.masked_fill(mask == 0, -1e9)
-            dist_ = torch.distributions.Categorical(logits=logits)
-            a = dist_.sample()
+                logits, v = pi_head(h), v_head(h).float().squeeze(1)
+            # masked categorical head on the bf16 logits (ongym_masked_categorical): one pass over the row, the exact masked
+            # distribution; the backward reads the packed mask it saved, so the next observation may overwrite `mask`
+            a, lp, _ = masked_categorical(env, logits, mask, seed=7)
             actions.copy_(a)
             env_step()
-            logps.append(dist_.log_prob(a)); values.append(v)
+            logps.append(lp); values.append(v)
             rewards.append(recs[:, r_off:r_off + 8].contiguous().view(torch.float64).squeeze(1).float())
             if len(rewards) == args.horizon:
                 ret, rets = torch.zeros(B, device=dev), []
