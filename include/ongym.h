@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ONGYM_ABI_VERSION 3
+#define ONGYM_ABI_VERSION 4
 
 enum {
     ONGYM_OK = 0,
@@ -297,23 +297,29 @@ int ongym_sample_actions(ongym_env *env, const uint8_t *mask, uint64_t seed, uin
  *             draw_index) countered by entry, in a domain of its own (not the uniform sampler's stream);
  *           ONGYM_HEAD_ARGMAX: the first valid entry with the largest logit (MaskableCategorical.mode(), deterministic=True);
  *           ONGYM_HEAD_EVALUATE: log-prob and entropy of the GIVEN actions (MaskablePPO's evaluate_actions); actions are read.
- * Outputs per row: actions (written in the first two modes), log_prob, entropy, lse (the masked log-sum-exp, kept for the
- * backward call), mask_bits uint32 [batch][ceil(n_actions/32)] (bit j of row r = mask[r][j] != 0); every output but actions
- * may be NULL.  Rows where only the reject entry is valid give (reject, 0, 0); rows with no valid entry (a caller error) give
- * the reject action and NaN log_prob / entropy / lse; in evaluate mode an action outside the mask gets log_prob = -inf.
+ * Outputs per row: actions (written in the first two modes), log_prob, entropy, row_stats float [batch][2] (the largest
+ * valid logit m and log sum_valid e^(x-m), kept for the backward call; log_prob = (x_a - m) - log sum, so it does not depend
+ * on a common offset of the row), mask_bits uint32 [batch][ceil(n_actions/32)] (bit j of row r = mask[r][j] != 0, padding
+ * bits 0); every output but actions may be NULL.  Rows where only the reject entry is valid give (reject, 0, 0); rows with no
+ * valid entry (a caller error) give the reject action and NaN log_prob / entropy / row_stats; in evaluate mode an action
+ * outside the mask gets log_prob = -inf.
+ * Non-finite logits in VALID entries: -inf means probability 0 (as torch's Categorical): every output is bit for bit the one
+ * of the same call with that entry masked (its evaluate log_prob is -inf, its gradient 0); a row whose valid entries are all
+ * -inf is a row with no valid entry.  NaN or +inf poisons its row: log_prob and entropy are NaN (in every mode), the sampled
+ * or argmax action is still an entry of the mask, and other rows are not affected.
  * Device pointers only: both calls fail with ONGYM_E_ARG unless cfg.io_device = 1.  Launched on the env's current stream
  * (ongym_set_stream), nothing synchronises. */
 enum { ONGYM_DTYPE_F32 = 0, ONGYM_DTYPE_BF16 = 1 };
 enum { ONGYM_HEAD_SAMPLE = 0, ONGYM_HEAD_ARGMAX = 1, ONGYM_HEAD_EVALUATE = 2 };
 int ongym_masked_categorical(ongym_env *env, const void *logits, int32_t dtype, const uint8_t *mask, int32_t mode,
                              uint64_t seed, uint64_t draw_index, int32_t *actions, float *log_prob, float *entropy,
-                             float *lse, uint32_t *mask_bits);
+                             float *row_stats, uint32_t *mask_bits);
 /* Gradient of  sum_r g_lp[r] log_prob[r] + g_H[r] entropy[r]  with respect to the logits of the forward call above, from the
- * saved mask bits, actions, lse and entropy (not the caller's mask, which the next observation overwrites):
- * grad_logits[r][j] = valid ? g_lp (delta_{j,a} - p_j) - g_H p_j (log p_j + H) : 0, written in the logits' dtype.  g_lp / g_H
- * (float [batch]) may be NULL (zero).  Same pointer, alignment and stream rules. */
+ * saved mask bits, actions, row_stats and entropy (not the caller's mask, which the next observation overwrites):
+ * grad_logits[r][j] = valid ? g_lp (delta_{j,a} - p_j) - g_H p_j (log p_j + H) : 0, written in the logits' dtype (a valid
+ * entry with a logit of -inf counts as masked: 0; p log p = 0 where p = 0).  g_lp / g_H (float [batch]) may be NULL (zero).  Same pointer, alignment and stream rules. */
 int ongym_masked_categorical_backward(ongym_env *env, const void *logits, int32_t dtype, const uint32_t *mask_bits,
-                                      const int32_t *actions, const float *lse, const float *entropy,
+                                      const int32_t *actions, const float *row_stats, const float *entropy,
                                       const float *grad_log_prob, const float *grad_entropy, void *grad_logits);
 
 /* Plugin-API queries on one replica (host buffers always): */

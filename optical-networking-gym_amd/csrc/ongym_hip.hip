@@ -1305,7 +1305,7 @@ static int head_check(ongym_env *env, const void *logits, int32_t dtype, const v
 
 int ongym_masked_categorical(ongym_env *env, const void *logits, int32_t dtype, const uint8_t *mask, int32_t mode,
                              uint64_t seed, uint64_t draw_index, int32_t *actions, float *log_prob, float *entropy,
-                             float *lse, uint32_t *mask_bits) {
+                             float *row_stats, uint32_t *mask_bits) {
     if (!env) return ONGYM_E_ARG;
     { int rc = head_check(env, logits, dtype, mask, 8); if (rc) return rc; }
     if (!actions) return fail_arg(env, "null actions");
@@ -1320,7 +1320,7 @@ int ongym_masked_categorical(ongym_env *env, const void *logits, int32_t dtype, 
 #define ONGYM_HEAD_FWD(DT, MODE)                                                                                           \
     hipLaunchKernelGGL((k_head_fwd<DT, MODE>), grid, block, shm, env->stream,                                              \
                        static_cast<const HeadElem<DT>::T *>(logits), mask, B, nact, seed, env->replica_base, draw_index,  \
-                       actions, log_prob, entropy, lse, mask_bits)
+                       actions, log_prob, entropy, row_stats, mask_bits)
 #define ONGYM_HEAD_FWD_MODES(DT)                                                                                           \
     if (mode == ONGYM_HEAD_SAMPLE) ONGYM_HEAD_FWD(DT, ONGYM_HEAD_SAMPLE);                                                  \
     else if (mode == ONGYM_HEAD_ARGMAX) ONGYM_HEAD_FWD(DT, ONGYM_HEAD_ARGMAX);                                             \
@@ -1334,11 +1334,11 @@ int ongym_masked_categorical(ongym_env *env, const void *logits, int32_t dtype, 
 }
 
 int ongym_masked_categorical_backward(ongym_env *env, const void *logits, int32_t dtype, const uint32_t *mask_bits,
-                                      const int32_t *actions, const float *lse, const float *entropy,
+                                      const int32_t *actions, const float *row_stats, const float *entropy,
                                       const float *grad_log_prob, const float *grad_entropy, void *grad_logits) {
     if (!env) return ONGYM_E_ARG;
     { int rc = head_check(env, logits, dtype, mask_bits, 4); if (rc) return rc; }
-    if (!actions || !lse || !entropy || !grad_logits) return fail_arg(env, "null actions / lse / entropy / grad_logits");
+    if (!actions || !row_stats || !entropy || !grad_logits) return fail_arg(env, "null actions / row_stats / entropy / grad_logits");
     if ((uintptr_t)grad_logits % 16) return fail_arg(env, "grad_logits must be 16-byte aligned");
     HIP_TRY(env, hipSetDevice(env->cfg.device));
     const Params &P = env->P;
@@ -1346,10 +1346,10 @@ int ongym_masked_categorical_backward(ongym_env *env, const void *logits, int32_
     const dim3 grid((B + kHeadWaves - 1) / kHeadWaves), block(64 * kHeadWaves);
     if (dtype == ONGYM_DTYPE_F32)
         hipLaunchKernelGGL((k_head_bwd<ONGYM_DTYPE_F32>), grid, block, 0, env->stream, static_cast<const float *>(logits),
-                           mask_bits, B, nact, actions, lse, entropy, grad_log_prob, grad_entropy, static_cast<float *>(grad_logits));
+                           mask_bits, B, nact, actions, row_stats, entropy, grad_log_prob, grad_entropy, static_cast<float *>(grad_logits));
     else
         hipLaunchKernelGGL((k_head_bwd<ONGYM_DTYPE_BF16>), grid, block, 0, env->stream, static_cast<const uint16_t *>(logits),
-                           mask_bits, B, nact, actions, lse, entropy, grad_log_prob, grad_entropy, static_cast<uint16_t *>(grad_logits));
+                           mask_bits, B, nact, actions, row_stats, entropy, grad_log_prob, grad_entropy, static_cast<uint16_t *>(grad_logits));
     HIP_TRY(env, hipGetLastError());
     return ONGYM_OK;
 }

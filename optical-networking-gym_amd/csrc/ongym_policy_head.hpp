@@ -4,10 +4,15 @@
 // examples/ONDM_2025/train_multi_masked_ppo.py), evaluated exactly: masked entries do not exist, whatever their logit holds.
 // One wavefront per row, one pass over the row:
 //   forward   online softmax  m = max x,  s = sum e^(x-m),  t = sum e^(x-m)(x-m)   (on a max move m -> m':
-//             t <- e^(m-m')(t + (m-m')s), s <- e^(m-m')s),  lse = m + log s,  H = log s - t/s;
+//             t <- e^(m-m')(t + (m-m')s), s <- e^(m-m')s),  log p_j = (x_j - m) - log s,  H = log s - t/s;
 //             sample mode draws by Gumbel-max in the same pass, argmax mode keeps the first largest valid logit;
-//             the chosen / given action's logit is read once more after the pass (one element per row)
-//   backward  grad_j = valid_j ? g_lp (delta_ja - p_j) - g_H p_j (log p_j + H) : 0,  p_j = e^(x_j - lse)
+//             the chosen / given action's logit is read once more after the pass (one element per row);
+//             the row stats (m, log s) are saved for the backward: x - m is exact near m, so log p does not lose
+//             ulp(m) to a rounded m + log s (shift invariance, as torch's log_softmax)
+//   backward  grad_j = valid_j ? g_lp (delta_ja - p_j) - g_H p_j (log p_j + H) : 0,  log p_j = (x_j - m) - log s
+// Non-finite valid logits: -inf adds e^-inf = 0 to s and nothing to t (no 0 * inf: the running max starts at -FLT_MAX, and
+// e^d d is taken at max(d, -FLT_MAX)), so the row is the one with that entry masked, bit for bit; its gradient is 0.
+// NaN or +inf makes s NaN; a state merges whenever s != 0, so the NaN reaches the row's log_prob and entropy.
 // The row length n = k*Mc*S + 1 is odd, so rows start at any element.  A lane works on CHUNKS of 8 elements aligned on
 // the GLOBAL element index (logits base 16-byte aligned, mask base 8-byte aligned: one 16 B (bf16) or two 16 B (f32) loads
 // plus one 8 B mask load per chunk); the first and last chunk of a row are partial and read element by element.
@@ -18,6 +23,7 @@
 // (head_gumbel).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <float.h>
 #include <stdint.h>
 
 #include "../../include/ongym.h"
@@ -87,10 +93,19 @@ __device__ static inline float head_gumbel(uint32_t bits24) {
 
 // Per-lane running state of the forward pass
 struct HeadAcc {
-    float m = -INFINITY, s = 0.f, t = 0.f;     // online softmax + entropy
+    float m = -FLT_MAX, s = 0.f, t = 0.f;      // online softmax + entropy (s = 0: nothing folded; s NaN: poisoned)
     float key = -INFINITY;                     // best Gumbel key / logit
     int idx = 0x7FFFFFFF;                      // its entry (first on ties)
 };
+
+// move the lane's max to mm > a.m.  d = -inf (an f32 overflow of the difference) gives r = 0: the guard keeps 0 * inf out of t.
+// A NaN s stays NaN.
+__device__ static inline void head_rescale(HeadAcc &a, float mm) {
+    const float d = a.m - mm, r = __expf(d);
+    a.t = r > 0.f ? r * (a.t + d * a.s) : 0.f;
+    a.s *= r;
+    a.m = mm;
+}
 
 // fold valid entries {x[e] : bit e of vb} at row entries j0 + e into the lane state
 template <int MODE>
@@ -98,12 +113,7 @@ __device__ static inline void head_fold(HeadAcc &a, const float x[8], uint32_t v
     float cm = -INFINITY;
 #pragma unroll
     for (int e = 0; e < 8; e++) cm = ((vb >> e) & 1u) ? fmaxf(cm, x[e]) : cm;
-    if (cm > a.m) {                            // the max moves: rescale (s = 0 before the first valid entry)
-        const float d = a.m - cm, r = a.s > 0.f ? __expf(d) : 0.f;
-        a.t = a.s > 0.f ? r * (a.t + d * a.s) : 0.f;
-        a.s *= r;
-        a.m = cm;
-    }
+    if (cm > a.m) head_rescale(a, cm);         // the max moves
     uint64_t hw[5];
     if (MODE == ONGYM_HEAD_SAMPLE) {
         const long long p0 = j0 >> 1;          // j0 >= 0 here; entries j0..j0+7 span pairs p0..p0+4
@@ -116,7 +126,7 @@ __device__ static inline void head_fold(HeadAcc &a, const float x[8], uint32_t v
         if (!((vb >> e) & 1u)) continue;
         const float d = x[e] - a.m, p = __expf(d);
         a.s += p;
-        a.t = fmaf(p, d, a.t);
+        a.t = fmaf(p, fmaxf(d, -FLT_MAX), a.t);        // x = -inf: p = 0, d = -inf
         const int j = (int)(j0 + e);
         float k = x[e];
         if (MODE == ONGYM_HEAD_SAMPLE) {
@@ -131,29 +141,24 @@ __device__ static inline void head_fold(HeadAcc &a, const float x[8], uint32_t v
 // the same for a partial chunk, element by element (any j0, some entries outside the row: vb already excludes them)
 template <int MODE>
 __device__ static inline void head_fold_one(HeadAcc &a, float x, long long j, uint64_t key) {
-    if (x > a.m) {
-        const float d = a.m - x, r = a.s > 0.f ? __expf(d) : 0.f;
-        a.t = a.s > 0.f ? r * (a.t + d * a.s) : 0.f;
-        a.s *= r;
-        a.m = x;
-    }
+    if (x > a.m) head_rescale(a, x);
     const float d = x - a.m, p = __expf(d);
     a.s += p;
-    a.t = fmaf(p, d, a.t);
+    a.t = fmaf(p, fmaxf(d, -FLT_MAX), a.t);
     float k = x;
     if (MODE == ONGYM_HEAD_SAMPLE) {
         const uint64_t w = ongym_mix64(key + ((uint64_t)(j >> 1) + 1) * 0x9E3779B97F4A7C15ull);
         k += head_gumbel((uint32_t)((((j & 1) ? w : (w >> 32)) & 0xFFFFFFFFull) >> 8));
     }
-    if (k > a.key || (k == a.key && j < a.idx)) { a.key = k; a.idx = (int)j; }
+    if (k > a.key) { a.key = k; a.idx = (int)j; }      // as in head_fold (a key of -inf is never taken)
 }
 
-// combine two lane states (b into a)
+// combine two lane states (b into a).  s != 0, not s > 0: a NaN s (a NaN or +inf logit) must reach the result.
 __device__ static inline void head_merge(HeadAcc &a, float m, float s, float t, float key, int idx) {
-    if (s > 0.f) {
-        if (a.s > 0.f) {
+    if (s != 0.f) {
+        if (a.s != 0.f) {
             const float mm = fmaxf(a.m, m), da = a.m - mm, db = m - mm, ra = __expf(da), rb = __expf(db);
-            a.t = ra * (a.t + da * a.s) + rb * (t + db * s);
+            a.t = (ra > 0.f ? ra * (a.t + da * a.s) : 0.f) + (rb > 0.f ? rb * (t + db * s) : 0.f);
             a.s = ra * a.s + rb * s;
             a.m = mm;
         } else { a.m = m; a.s = s; a.t = t; }
@@ -168,7 +173,7 @@ __global__ __launch_bounds__(64 * kHeadWaves) void k_head_fwd(const typename Hea
                                                               const uint8_t *__restrict__ mask, int batch, int nact,
                                                               uint64_t seed, uint64_t replica_base, uint64_t draw,
                                                               int32_t *__restrict__ actions, float *__restrict__ log_prob,
-                                                              float *__restrict__ entropy, float *__restrict__ lse_out,
+                                                              float *__restrict__ entropy, float *__restrict__ stats_out,
                                                               uint32_t *__restrict__ bits_out) {
     using E = HeadElem<DT>;
     extern __shared__ __align__(16) uint32_t head_lds[];
@@ -229,30 +234,34 @@ __global__ __launch_bounds__(64 * kHeadWaves) void k_head_fwd(const typename Hea
         for (int i = lane; i < nw; i += 64) dst[i] = bits[i];
     }
     if (lane != 0) return;
-    const bool any = a.s > 0.f;
-    const float lse = any ? a.m + __logf(a.s) : NAN;
-    const float H = any ? __logf(a.s) - a.t / a.s : NAN;
+    const bool any = a.s != 0.f;                              // NaN s (poisoned row) included
+    const bool ok = a.s > 0.f;                                // some finite valid logit, no NaN / +inf
+    const float ls = __logf(a.s);
+    const float H = any ? ls - a.t / a.s : NAN;
     int act;
     float lp;
     if (MODE == ONGYM_HEAD_EVALUATE) {
         act = actions[row];
-        lp = (act >= 0 && act < nact && mask[g0 + act]) ? E::get(logits, g0 + act) - lse : -INFINITY;
-        if (!any) lp = NAN;
+        lp = (act >= 0 && act < nact && mask[g0 + act]) ? (E::get(logits, g0 + act) - a.m) - ls : -INFINITY;
     } else {
-        act = (any && a.idx < nact) ? a.idx : nact - 1;        // no valid entry (a caller error): reject, NaN
-        lp = any ? E::get(logits, g0 + act) - lse : NAN;
+        act = (any && a.idx < nact) ? a.idx : nact - 1;        // no valid finite entry (a caller error): reject, NaN
+        lp = (E::get(logits, g0 + act) - a.m) - ls;
         actions[row] = act;
     }
+    if (!ok) lp = NAN;
     if (log_prob) log_prob[row] = lp;
     if (entropy) entropy[row] = H;
-    if (lse_out) lse_out[row] = lse;
+    if (stats_out) {
+        stats_out[2 * (size_t)row] = any ? a.m : NAN;
+        stats_out[2 * (size_t)row + 1] = any ? ls : NAN;
+    }
 }
 
 // Backward: same geometry, no LDS.  g_lp / g_H may be null (zero).
 template <int DT>
 __global__ __launch_bounds__(64 * kHeadWaves) void k_head_bwd(const typename HeadElem<DT>::T *__restrict__ logits,
                                                               const uint32_t *__restrict__ bits, int batch, int nact,
-                                                              const int32_t *__restrict__ actions, const float *__restrict__ lse,
+                                                              const int32_t *__restrict__ actions, const float *__restrict__ stats,
                                                               const float *__restrict__ entropy, const float *__restrict__ g_lp,
                                                               const float *__restrict__ g_H,
                                                               typename HeadElem<DT>::T *__restrict__ grad) {
@@ -266,7 +275,7 @@ __global__ __launch_bounds__(64 * kHeadWaves) void k_head_bwd(const typename Hea
     const int s0 = (int)(g0 & 7);
     const int nch = (s0 + nact + 7) >> 3;
     const long long gc = g0 - s0;
-    const float L = lse[row], H = entropy[row];
+    const float M = stats[2 * (size_t)row], LS = stats[2 * (size_t)row + 1], H = entropy[row];
     const float glp = g_lp ? g_lp[row] : 0.f, gH = g_H ? g_H[row] : 0.f;
     const int act = actions[row];
     for (int c = lane; c < nch; c += 64) {
@@ -282,9 +291,10 @@ __global__ __launch_bounds__(64 * kHeadWaves) void k_head_bwd(const typename Hea
                 E::load8(logits, gc + 8ll * c, x);
 #pragma unroll
                 for (int e = 0; e < 8; e++) {
-                    const float lp = x[e] - L, p = __expf(lp);
+                    const float lp = (x[e] - M) - LS, p = __expf(lp);
                     const float d = (j0 + e == act) ? 1.f : 0.f;
-                    g[e] = ((vb >> e) & 1u) ? glp * (d - p) - gH * p * (lp + H) : 0.f;
+                    const float h = p == 0.f ? 0.f : p * (lp + H);        // p = 0: lp may be -inf
+                    g[e] = (((vb >> e) & 1u) && x[e] != -INFINITY) ? glp * (d - p) - gH * h : 0.f;
                 }
             } else {
 #pragma unroll
@@ -296,9 +306,10 @@ __global__ __launch_bounds__(64 * kHeadWaves) void k_head_bwd(const typename Hea
                 const long long j = j0 + e;
                 if (j < 0 || j >= nact) continue;
                 float gv = 0.f;
-                if ((rb[j >> 5] >> (j & 31)) & 1u) {
-                    const float lp = E::get(logits, g0 + j) - L, p = __expf(lp);
-                    gv = glp * ((j == act ? 1.f : 0.f) - p) - gH * p * (lp + H);
+                const float x = E::get(logits, g0 + j);
+                if (((rb[j >> 5] >> (j & 31)) & 1u) && x != -INFINITY) {
+                    const float lp = (x - M) - LS, p = __expf(lp);
+                    gv = glp * ((j == act ? 1.f : 0.f) - p) - gH * (p == 0.f ? 0.f : p * (lp + H));
                 }
                 E::put(grad, g0 + j, gv);
             }

@@ -12,7 +12,7 @@ import numpy as np
 
 from ._tables import StaticTables, cumulative, modulation_arrays
 
-ABI_VERSION = 3
+ABI_VERSION = 4
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC_DIR = os.path.join(os.path.dirname(PKG_DIR), "csrc")
 HIP_LIB_PATH = os.path.join(CSRC_DIR, "libongym_hip.so")

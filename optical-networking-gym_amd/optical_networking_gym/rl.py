@@ -7,6 +7,11 @@ logits with masked entries filled with -1e8).  It computes the exact masked dist
 normalised over the valid entries only and the entropy is -sum_valid p log p.  `log_prob` and `entropy` carry gradients to
 the logits through ongym_masked_categorical_backward.
 
+Non-finite logits in valid entries: -inf means probability 0, as in torch's Categorical (the same outputs, bit for bit, as with
+that entry masked; its gradient is 0); a row whose valid entries are all -inf is a row with no valid entry (reject action, NaN
+log_prob and entropy).  NaN or +inf makes that row's log_prob and entropy NaN, so a diverged policy shows; its action is still
+a valid entry and the other rows are not affected.
+
     obs, mask = ...                                         # ongym_observe into torch tensors (io_device=True)
     logits = policy(obs)                                    # [B, n_actions], float32 or bfloat16
     actions, log_prob, entropy = masked_categorical(env, logits, mask)            # MaskableCategorical.sample()
@@ -47,29 +52,29 @@ class _MaskedCategorical(torch.autograd.Function):
         out_actions = actions.clone() if actions is not None else torch.empty(B, dtype=torch.int32, device=dev)
         log_prob = torch.empty(B, dtype=torch.float32, device=dev)
         entropy = torch.empty(B, dtype=torch.float32, device=dev)
-        lse = torch.empty(B, dtype=torch.float32, device=dev)
+        stats = torch.empty((B, 2), dtype=torch.float32, device=dev)     # per row: max valid logit, log sum of e^(x - max)
         # the packed mask is saved, not the caller's mask: the next observation overwrites that buffer through a raw pointer,
         # which torch's version counter cannot see
         bits = torch.empty((B, (n + 31) // 32), dtype=torch.int32, device=dev)
         env._check(env.lib.ongym_masked_categorical(env._h, _ptr(logits), _DTYPES[logits.dtype], _ptr(mask), int(mode),
                                                     C.c_uint64(seed), C.c_uint64(draw_index), _ptr(out_actions),
-                                                    _ptr(log_prob), _ptr(entropy), _ptr(lse), _ptr(bits)),
+                                                    _ptr(log_prob), _ptr(entropy), _ptr(stats), _ptr(bits)),
                    "ongym_masked_categorical")
         ctx.env = env
-        ctx.save_for_backward(logits, bits, out_actions, lse, entropy)
+        ctx.save_for_backward(logits, bits, out_actions, stats, entropy)
         ctx.mark_non_differentiable(out_actions)
         return out_actions, log_prob, entropy
 
     @staticmethod
     def backward(ctx, g_actions, g_log_prob, g_entropy):
-        logits, bits, actions, lse, entropy = ctx.saved_tensors
+        logits, bits, actions, stats, entropy = ctx.saved_tensors
         env = ctx.env
         _check_stream(env)
         g_lp = None if g_log_prob is None else g_log_prob.to(torch.float32).contiguous()
         g_h = None if g_entropy is None else g_entropy.to(torch.float32).contiguous()
         grad = torch.empty_like(logits, memory_format=torch.contiguous_format)
         env._check(env.lib.ongym_masked_categorical_backward(env._h, _ptr(logits), _DTYPES[logits.dtype], _ptr(bits),
-                                                             _ptr(actions), _ptr(lse), _ptr(entropy), _ptr(g_lp), _ptr(g_h),
+                                                             _ptr(actions), _ptr(stats), _ptr(entropy), _ptr(g_lp), _ptr(g_h),
                                                              _ptr(grad)),
                    "ongym_masked_categorical_backward")
         return grad, None, None, None, None, None, None

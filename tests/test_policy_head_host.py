@@ -54,3 +54,51 @@ def test_rl_module_imports_and_validates():
         masked_categorical(env, logits.to(torch.float16), mask)
     with pytest.raises(ValueError, match="logits"):       # a CPU tensor is on the wrong device
         masked_categorical(env, logits, mask)
+
+
+def test_abi_version_and_row_stats_in_the_header():
+    """ABI 4: the per-row value saved for the backward is two floats (max valid logit, log sum), not one lse"""
+    import os
+    import re
+    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "ongym.h")).read()
+    assert int(re.search(r"#define ONGYM_ABI_VERSION (\d+)", header).group(1)) == nat.ABI_VERSION == 4
+    assert nat.load_library().ongym_abi_version() == 4
+    for name in NEW:
+        decl = re.search(name + r"\s*\(([^)]*)\)", header).group(1)
+        assert "float *row_stats" in decl and "lse" not in decl, name
+    assert "row_stats float [batch][2]" in header
+
+
+class _Ctx:
+    def save_for_backward(self, *t):
+        self.saved = t
+
+    def mark_non_differentiable(self, *t):
+        pass
+
+
+class _RecordingLib:
+    """stands in for the library: records the buffers ongym_masked_categorical is given"""
+    def __init__(self):
+        self.calls = []
+
+    def ongym_masked_categorical(self, *args):
+        self.calls.append(args)
+        return 0
+
+
+def test_rl_forward_allocates_two_row_stats_per_row():
+    import torch
+    from optical_networking_gym.rl import _MaskedCategorical
+    env = _FakeEnv(io_device=True)
+    env.lib, env._h = _RecordingLib(), None
+    env._check = lambda rc, what: None
+    B, n = env.batch_size, env.num_actions
+    ctx = _Ctx()
+    logits, mask = torch.zeros((B, n)), torch.ones((B, n), dtype=torch.uint8)
+    _MaskedCategorical.forward(ctx, logits, env, mask, None, nat.HEAD_SAMPLE, 0, 0)
+    saved_logits, bits, actions, stats, entropy = ctx.saved
+    assert stats.shape == (B, 2) and stats.dtype == torch.float32 and stats.is_contiguous()
+    assert bits.shape == (B, (n + 31) // 32) and actions.shape == (B,) and entropy.shape == (B,)
+    args = env.lib.calls[0]
+    assert len(args) == 12 and args[10].value == stats.data_ptr() and args[11].value == bits.data_ptr()

@@ -51,7 +51,8 @@ def main():
     valid_frac = float(mask.float().mean())
     W = (n + 31) // 32
     acts = torch.empty(B, dtype=torch.int32, device=dev)
-    lp, H, lse = (torch.empty(B, device=dev) for _ in range(3))
+    lp, H = (torch.empty(B, device=dev) for _ in range(2))
+    stats = torch.empty((B, 2), device=dev)      # row stats: max valid logit, log sum
     bits = torch.empty((B, W), dtype=torch.int32, device=dev)
     g_lp, g_H = torch.randn(B, device=dev), torch.randn(B, device=dev)
     p = lambda t: C.c_void_p(t.data_ptr())       # noqa: E731
@@ -80,12 +81,12 @@ def main():
         def head(mode):
             def f():
                 env._check(env.lib.ongym_masked_categorical(env._h, p(logits), code, p(mask), mode, 0, draw[0], p(acts), p(lp), p(H),
-                                                             p(lse), p(bits)), "head")
+                                                             p(stats), p(bits)), "head")
                 draw[0] += 1
             return f
 
         def head_bwd():
-            env._check(env.lib.ongym_masked_categorical_backward(env._h, p(logits), code, p(bits), p(acts), p(lse), p(H), p(g_lp),
+            env._check(env.lib.ongym_masked_categorical_backward(env._h, p(logits), code, p(bits), p(acts), p(stats), p(H), p(g_lp),
                                                                  p(g_H), p(grad)), "head bwd")
 
         def torch_fwd(sample):
@@ -106,7 +107,7 @@ def main():
             x_req.grad = None
 
         name = "bf16" if dt == torch.bfloat16 else "f32"
-        head(nat.HEAD_SAMPLE)()        # actions / lse / entropy / bits for the evaluate and backward timings
+        head(nat.HEAD_SAMPLE)()        # actions / row stats / entropy / bits for the evaluate and backward timings
         for what, fn, nbytes in (("sample", head(nat.HEAD_SAMPLE), fwd_bytes), ("argmax", head(nat.HEAD_ARGMAX), fwd_bytes),
                                  ("evaluate", head(nat.HEAD_EVALUATE), fwd_bytes), ("backward", head_bwd, bwd_bytes)):
             ms = timed(fn)
