@@ -322,6 +322,40 @@ int ongym_masked_categorical_backward(ongym_env *env, const void *logits, int32_
                                       const int32_t *actions, const float *row_stats, const float *entropy,
                                       const float *grad_log_prob, const float *grad_entropy, void *grad_logits);
 
+/* The head on ANY number of rows (a PPO minibatch gathered from a rollout), with the mask given as bytes or packed bits.
+ * Semantics are those of the pair above with `rows` (>= 0; 0 launches nothing) in place of cfg.batch: logits, mask, outputs
+ * and grad_logits have `rows` rows, and in sample mode row r draws from the stream of global replica replica_base + r.  For
+ * rows == cfg.batch and ONGYM_MASK_BYTES the outputs are bit for bit those of ongym_masked_categorical.
+ *   mask_format  ONGYM_MASK_BYTES: mask is uint8 [rows][n_actions], 8-byte aligned (as above);
+ *                ONGYM_MASK_BITS:  mask is uint32 [rows][ceil(n_actions/32)], 4-byte aligned, in the layout the forward writes
+ *                to mask_bits (bit j of row r = entry j; padding bits are ignored); mask_bits out must then be NULL.
+ * A rollout keeps the 8x smaller bits of every step (mask_bits out of the sampling call) and evaluates minibatches from them. */
+enum { ONGYM_MASK_BYTES = 0, ONGYM_MASK_BITS = 1 };
+int ongym_masked_categorical_rows(ongym_env *env, int32_t rows, const void *logits, int32_t dtype,
+                                  const void *mask, int32_t mask_format, int32_t mode, uint64_t seed,
+                                  uint64_t draw_index, int32_t *actions, float *log_prob, float *entropy,
+                                  float *row_stats, uint32_t *mask_bits);
+int ongym_masked_categorical_backward_rows(ongym_env *env, int32_t rows, const void *logits, int32_t dtype,
+                                           const uint32_t *mask_bits, const int32_t *actions, const float *row_stats,
+                                           const float *entropy, const float *grad_log_prob,
+                                           const float *grad_entropy, void *grad_logits);
+
+/* Generalised advantage estimation over a rollout (SB3's RolloutBuffer.compute_returns_and_advantage, as MaskablePPO runs it),
+ * the episode ends taken from the step records:
+ *   recs         ongym_step_rec [steps][batch]: `steps` calls of ongym_step_actions writing consecutive slices, 8-byte aligned
+ *   values       float [steps][batch]: the value estimate of each step's observation
+ *   last_values  float [batch]: the value of the observation after the last step
+ * For t = steps-1 .. 0 (A = 0 before the first iteration):
+ *   nnt   = 1 - recs[t][b].terminated
+ *   vnext = t == steps-1 ? last_values[b] : values[t+1][b]
+ *   delta = (float)recs[t][b].reward + gamma * vnext * nnt - values[t][b]
+ *   A     = delta + gamma * gae_lambda * nnt * A;   advantages[t][b] = A;  returns[t][b] = A + values[t][b]
+ * f32 arithmetic, in any summation order; NaN / inf as the sequential recurrence (0 * NaN = NaN: a NaN crosses a termination).
+ * Device buffers only (cfg.io_device = 1), f32 buffers 4-byte aligned; outputs must not overlap each other or an input.
+ * ONGYM_E_ARG also for steps < 1 and gamma or gae_lambda outside [0, 1].  On the env's stream, nothing synchronises. */
+int ongym_gae(ongym_env *env, int32_t steps, const ongym_step_rec *recs, const float *values,
+              const float *last_values, float gamma, float gae_lambda, float *advantages, float *returns);
+
 /* Plugin-API queries on one replica (host buffers always): */
 /* QRMSAEnv.get_available_slots(path) (qrmsa.pyx:1482-1512): out[n_slots], 1 = free on every link of the path */
 int ongym_query_available(ongym_env *env, int32_t replica, int32_t path_id, int32_t *out);

@@ -19,6 +19,7 @@
 #include "ongym_fast.hpp"      // fast_lds_bytes, PathRec (the kernels themselves: ongym_fast.hip)
 #include "ongym_scored.hpp"
 #include "ongym_policy_head.hpp"   // masked categorical action head (ongym_masked_categorical)
+#include "ongym_gae.hpp"           // GAE over a rollout (ongym_gae)
 
 using namespace ongym;
 
@@ -1303,32 +1304,73 @@ static int head_check(ongym_env *env, const void *logits, int32_t dtype, const v
     return ONGYM_OK;
 }
 
+int ongym_masked_categorical_rows(ongym_env *env, int32_t rows, const void *logits, int32_t dtype, const void *mask,
+                                  int32_t mask_format, int32_t mode, uint64_t seed, uint64_t draw_index, int32_t *actions,
+                                  float *log_prob, float *entropy, float *row_stats, uint32_t *mask_bits) {
+    if (!env) return ONGYM_E_ARG;
+    if (mask_format != ONGYM_MASK_BYTES && mask_format != ONGYM_MASK_BITS) return fail_arg(env, "unknown mask format");
+    { int rc = head_check(env, logits, dtype, mask, mask_format == ONGYM_MASK_BITS ? 4 : 8); if (rc) return rc; }
+    if (!actions) return fail_arg(env, "null actions");
+    if (mode < ONGYM_HEAD_SAMPLE || mode > ONGYM_HEAD_EVALUATE) return fail_arg(env, "unknown head mode");
+    if (rows < 0) return fail_arg(env, "negative row count");
+    if (mask_format == ONGYM_MASK_BITS && mask_bits) return fail_arg(env, "mask_bits out must be NULL when the mask is packed bits");
+    const Params &P = env->P;
+    const int nact = P.k_paths * P.n_mods_consider * P.n_slots + 1;
+    const size_t lds = (size_t)kHeadWaves * ((nact + 31) / 32) * 4;
+    if (lds > 64 * 1024) return fail_arg(env, "n_actions too large for the masked categorical head", ONGYM_E_LIMIT);
+    if (rows == 0) return ONGYM_OK;
+    HIP_TRY(env, hipSetDevice(env->cfg.device));
+    const dim3 grid((rows + kHeadWaves - 1) / kHeadWaves), block(64 * kHeadWaves);
+    const size_t shm = mask_bits ? lds : 0;
+#define ONGYM_HEAD_FWD(DT, MODE, MF)                                                                                       \
+    hipLaunchKernelGGL((k_head_fwd<DT, MODE, MF>), grid, block, shm, env->stream,                                          \
+                       static_cast<const HeadElem<DT>::T *>(logits), static_cast<const HeadMask<MF>::T *>(mask), rows,    \
+                       nact, seed, env->replica_base, draw_index, actions, log_prob, entropy, row_stats, mask_bits)
+#define ONGYM_HEAD_FWD_MODES(DT, MF)                                                                                       \
+    if (mode == ONGYM_HEAD_SAMPLE) ONGYM_HEAD_FWD(DT, ONGYM_HEAD_SAMPLE, MF);                                              \
+    else if (mode == ONGYM_HEAD_ARGMAX) ONGYM_HEAD_FWD(DT, ONGYM_HEAD_ARGMAX, MF);                                         \
+    else ONGYM_HEAD_FWD(DT, ONGYM_HEAD_EVALUATE, MF)
+    if (mask_format == ONGYM_MASK_BYTES) {
+        if (dtype == ONGYM_DTYPE_F32) { ONGYM_HEAD_FWD_MODES(ONGYM_DTYPE_F32, ONGYM_MASK_BYTES); }
+        else { ONGYM_HEAD_FWD_MODES(ONGYM_DTYPE_BF16, ONGYM_MASK_BYTES); }
+    } else {
+        if (dtype == ONGYM_DTYPE_F32) { ONGYM_HEAD_FWD_MODES(ONGYM_DTYPE_F32, ONGYM_MASK_BITS); }
+        else { ONGYM_HEAD_FWD_MODES(ONGYM_DTYPE_BF16, ONGYM_MASK_BITS); }
+    }
+#undef ONGYM_HEAD_FWD_MODES
+#undef ONGYM_HEAD_FWD
+    HIP_TRY(env, hipGetLastError());
+    return ONGYM_OK;
+}
+
 int ongym_masked_categorical(ongym_env *env, const void *logits, int32_t dtype, const uint8_t *mask, int32_t mode,
                              uint64_t seed, uint64_t draw_index, int32_t *actions, float *log_prob, float *entropy,
                              float *row_stats, uint32_t *mask_bits) {
     if (!env) return ONGYM_E_ARG;
-    { int rc = head_check(env, logits, dtype, mask, 8); if (rc) return rc; }
-    if (!actions) return fail_arg(env, "null actions");
-    if (mode < ONGYM_HEAD_SAMPLE || mode > ONGYM_HEAD_EVALUATE) return fail_arg(env, "unknown head mode");
+    return ongym_masked_categorical_rows(env, env->P.batch, logits, dtype, mask, ONGYM_MASK_BYTES, mode, seed, draw_index,
+                                         actions, log_prob, entropy, row_stats, mask_bits);
+}
+
+int ongym_masked_categorical_backward_rows(ongym_env *env, int32_t rows, const void *logits, int32_t dtype,
+                                           const uint32_t *mask_bits, const int32_t *actions, const float *row_stats,
+                                           const float *entropy, const float *grad_log_prob, const float *grad_entropy,
+                                           void *grad_logits) {
+    if (!env) return ONGYM_E_ARG;
+    { int rc = head_check(env, logits, dtype, mask_bits, 4); if (rc) return rc; }
+    if (!actions || !row_stats || !entropy || !grad_logits) return fail_arg(env, "null actions / row_stats / entropy / grad_logits");
+    if ((uintptr_t)grad_logits % 16) return fail_arg(env, "grad_logits must be 16-byte aligned");
+    if (rows < 0) return fail_arg(env, "negative row count");
+    if (rows == 0) return ONGYM_OK;
     HIP_TRY(env, hipSetDevice(env->cfg.device));
     const Params &P = env->P;
-    const int nact = P.k_paths * P.n_mods_consider * P.n_slots + 1, B = P.batch;
-    const size_t lds = (size_t)kHeadWaves * ((nact + 31) / 32) * 4;
-    if (lds > 64 * 1024) return fail_arg(env, "n_actions too large for the masked categorical head", ONGYM_E_LIMIT);
-    const dim3 grid((B + kHeadWaves - 1) / kHeadWaves), block(64 * kHeadWaves);
-    const size_t shm = mask_bits ? lds : 0;
-#define ONGYM_HEAD_FWD(DT, MODE)                                                                                           \
-    hipLaunchKernelGGL((k_head_fwd<DT, MODE>), grid, block, shm, env->stream,                                              \
-                       static_cast<const HeadElem<DT>::T *>(logits), mask, B, nact, seed, env->replica_base, draw_index,  \
-                       actions, log_prob, entropy, row_stats, mask_bits)
-#define ONGYM_HEAD_FWD_MODES(DT)                                                                                           \
-    if (mode == ONGYM_HEAD_SAMPLE) ONGYM_HEAD_FWD(DT, ONGYM_HEAD_SAMPLE);                                                  \
-    else if (mode == ONGYM_HEAD_ARGMAX) ONGYM_HEAD_FWD(DT, ONGYM_HEAD_ARGMAX);                                             \
-    else ONGYM_HEAD_FWD(DT, ONGYM_HEAD_EVALUATE)
-    if (dtype == ONGYM_DTYPE_F32) { ONGYM_HEAD_FWD_MODES(ONGYM_DTYPE_F32); }
-    else { ONGYM_HEAD_FWD_MODES(ONGYM_DTYPE_BF16); }
-#undef ONGYM_HEAD_FWD_MODES
-#undef ONGYM_HEAD_FWD
+    const int nact = P.k_paths * P.n_mods_consider * P.n_slots + 1;
+    const dim3 grid((rows + kHeadWaves - 1) / kHeadWaves), block(64 * kHeadWaves);
+    if (dtype == ONGYM_DTYPE_F32)
+        hipLaunchKernelGGL((k_head_bwd<ONGYM_DTYPE_F32>), grid, block, 0, env->stream, static_cast<const float *>(logits),
+                           mask_bits, rows, nact, actions, row_stats, entropy, grad_log_prob, grad_entropy, static_cast<float *>(grad_logits));
+    else
+        hipLaunchKernelGGL((k_head_bwd<ONGYM_DTYPE_BF16>), grid, block, 0, env->stream, static_cast<const uint16_t *>(logits),
+                           mask_bits, rows, nact, actions, row_stats, entropy, grad_log_prob, grad_entropy, static_cast<uint16_t *>(grad_logits));
     HIP_TRY(env, hipGetLastError());
     return ONGYM_OK;
 }
@@ -1337,19 +1379,39 @@ int ongym_masked_categorical_backward(ongym_env *env, const void *logits, int32_
                                       const int32_t *actions, const float *row_stats, const float *entropy,
                                       const float *grad_log_prob, const float *grad_entropy, void *grad_logits) {
     if (!env) return ONGYM_E_ARG;
-    { int rc = head_check(env, logits, dtype, mask_bits, 4); if (rc) return rc; }
-    if (!actions || !row_stats || !entropy || !grad_logits) return fail_arg(env, "null actions / row_stats / entropy / grad_logits");
-    if ((uintptr_t)grad_logits % 16) return fail_arg(env, "grad_logits must be 16-byte aligned");
+    return ongym_masked_categorical_backward_rows(env, env->P.batch, logits, dtype, mask_bits, actions, row_stats, entropy,
+                                                  grad_log_prob, grad_entropy, grad_logits);
+}
+
+// GAE over a rollout (csrc/ongym_gae.hpp)
+static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+
+int ongym_gae(ongym_env *env, int32_t steps, const ongym_step_rec *recs, const float *values, const float *last_values,
+              float gamma, float gae_lambda, float *advantages, float *returns) {
+    if (!env) return ONGYM_E_ARG;
+    if (!env->cfg.io_device) return fail_arg(env, "ongym_gae takes device buffers: needs cfg.io_device = 1");
+    if (steps < 1) return fail_arg(env, "steps must be >= 1");
+    if (!recs || !values || !last_values || !advantages || !returns) return fail_arg(env, "null recs / values / last_values / outputs");
+    if (!(gamma >= 0.f && gamma <= 1.f) || !(gae_lambda >= 0.f && gae_lambda <= 1.f))
+        return fail_arg(env, "gamma and gae_lambda must lie in [0, 1]");
+    if ((uintptr_t)recs % 8) return fail_arg(env, "recs must be 8-byte aligned");
+    if ((uintptr_t)values % 4 || (uintptr_t)last_values % 4 || (uintptr_t)advantages % 4 || (uintptr_t)returns % 4)
+        return fail_arg(env, "values / last_values / advantages / returns must be 4-byte aligned");
+    const int B = env->P.batch;
+    const size_t n = (size_t)steps * B, nf = n * sizeof(float);
+    const struct { const void *p; size_t bytes; } in[] = {{recs, n * sizeof(ongym_step_rec)}, {values, nf}, {last_values, (size_t)B * 4},
+                                                          {returns, nf}};
+    for (const auto &r : in)
+        if (ranges_overlap(advantages, nf, r.p, r.bytes)) return fail_arg(env, "advantages overlaps another buffer");
+    for (int i = 0; i < 3; i++)
+        if (ranges_overlap(returns, nf, in[i].p, in[i].bytes)) return fail_arg(env, "returns overlaps another buffer");
     HIP_TRY(env, hipSetDevice(env->cfg.device));
-    const Params &P = env->P;
-    const int nact = P.k_paths * P.n_mods_consider * P.n_slots + 1, B = P.batch;
-    const dim3 grid((B + kHeadWaves - 1) / kHeadWaves), block(64 * kHeadWaves);
-    if (dtype == ONGYM_DTYPE_F32)
-        hipLaunchKernelGGL((k_head_bwd<ONGYM_DTYPE_F32>), grid, block, 0, env->stream, static_cast<const float *>(logits),
-                           mask_bits, B, nact, actions, row_stats, entropy, grad_log_prob, grad_entropy, static_cast<float *>(grad_logits));
-    else
-        hipLaunchKernelGGL((k_head_bwd<ONGYM_DTYPE_BF16>), grid, block, 0, env->stream, static_cast<const uint16_t *>(logits),
-                           mask_bits, B, nact, actions, row_stats, entropy, grad_log_prob, grad_entropy, static_cast<uint16_t *>(grad_logits));
+    const int waves = std::min(kGaeWaves, (steps + kGaeChunk - 1) / kGaeChunk);
+    hipLaunchKernelGGL(k_gae, dim3((B + 63) / 64), dim3(64 * waves), 0, env->stream, reinterpret_cast<const uint8_t *>(recs),
+                       values, last_values, steps, B, waves, gamma, gamma * gae_lambda, advantages, returns);
     HIP_TRY(env, hipGetLastError());
     return ONGYM_OK;
 }

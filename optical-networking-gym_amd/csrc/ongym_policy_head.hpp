@@ -16,6 +16,8 @@
 // The row length n = k*Mc*S + 1 is odd, so rows start at any element.  A lane works on CHUNKS of 8 elements aligned on
 // the GLOBAL element index (logits base 16-byte aligned, mask base 8-byte aligned: one 16 B (bf16) or two 16 B (f32) loads
 // plus one 8 B mask load per chunk); the first and last chunk of a row are partial and read element by element.
+// The forward also reads the mask as packed bits (HeadMask<ONGYM_MASK_BITS>, ongym_masked_categorical_rows): a chunk's 8 bits
+// are cut from one or two words, as the backward cuts them.  The row count is an argument of both kernels (any R).
 // Uniforms of the Gumbel draws: the counter-based generator of include/ongym_traffic.h.  Key of (row, draw) =
 // stream_key(stream_key(seed ^ kHeadDomain, global replica), draw_index): every draw is a stream of its own, so the counters
 // of one draw run 0, 1, 2, ... (a counter of draw * 2^32 + pair leaves the low half of the finaliser's input the same in
@@ -166,16 +168,46 @@ __device__ static inline void head_merge(HeadAcc &a, float m, float s, float t, 
     if (key > a.key || (key == a.key && idx < a.idx)) { a.key = key; a.idx = idx; }
 }
 
-// Forward: grid (ceil(B / kHeadWaves)), block 64 * kHeadWaves, dynamic LDS kHeadWaves * nwords * 4 (mask bits).
-// MODE: ONGYM_HEAD_SAMPLE / _ARGMAX / _EVALUATE (actions read).
-template <int DT, int MODE>
+// 8 bits of a packed row (entries j0 .. j0+7, 0 <= j0, j0 + 8 <= nact): they may straddle two words, and word w + 1 exists
+// whenever they do
+__device__ static inline uint32_t head_bits8(const uint32_t *rb, long long j0) {
+    const int w = (int)(j0 >> 5), sh = (int)(j0 & 31);
+    uint64_t v = rb[w];
+    if (sh > 24) v |= (uint64_t)rb[w + 1] << 32;
+    return (uint32_t)(v >> sh) & 0xFFu;
+}
+
+// The caller's mask in either format (ONGYM_MASK_BYTES: uint8 [rows][nact]; ONGYM_MASK_BITS: uint32 [rows][nw], the layout
+// the forward writes to mask_bits).  `full` reads the 8 entries of a whole chunk, `one` a single entry of the row.
+template <int MF> struct HeadMask;
+template <> struct HeadMask<ONGYM_MASK_BYTES> {
+    using T = uint8_t;
+    __device__ static inline uint32_t full(const uint8_t *m, long long gc8, long long, long long, int) {
+        return head_mask_bits(*reinterpret_cast<const uint2 *>(m + gc8));
+    }
+    __device__ static inline bool one(const uint8_t *m, long long g0, long long, long long j, int) { return m[g0 + j] != 0; }
+};
+template <> struct HeadMask<ONGYM_MASK_BITS> {
+    using T = uint32_t;
+    __device__ static inline uint32_t full(const uint32_t *m, long long, long long row, long long j0, int nw) {
+        return head_bits8(m + row * nw, j0);
+    }
+    __device__ static inline bool one(const uint32_t *m, long long, long long row, long long j, int nw) {
+        return (m[row * nw + (j >> 5)] >> (j & 31)) & 1u;
+    }
+};
+
+// Forward: grid (ceil(rows / kHeadWaves)), block 64 * kHeadWaves, dynamic LDS kHeadWaves * nwords * 4 (mask bits out).
+// MODE: ONGYM_HEAD_SAMPLE / _ARGMAX / _EVALUATE (actions read).  MF: format of the caller's mask (bits_out is null with bits).
+template <int DT, int MODE, int MF>
 __global__ __launch_bounds__(64 * kHeadWaves) void k_head_fwd(const typename HeadElem<DT>::T *__restrict__ logits,
-                                                              const uint8_t *__restrict__ mask, int batch, int nact,
+                                                              const typename HeadMask<MF>::T *__restrict__ mask, int batch, int nact,
                                                               uint64_t seed, uint64_t replica_base, uint64_t draw,
                                                               int32_t *__restrict__ actions, float *__restrict__ log_prob,
                                                               float *__restrict__ entropy, float *__restrict__ stats_out,
                                                               uint32_t *__restrict__ bits_out) {
     using E = HeadElem<DT>;
+    using M = HeadMask<MF>;
     extern __shared__ __align__(16) uint32_t head_lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int row = blockIdx.x * kHeadWaves + wave;
@@ -197,7 +229,7 @@ __global__ __launch_bounds__(64 * kHeadWaves) void k_head_fwd(const typename Hea
             uint32_t vb;
             float x[8];
             if (j0 >= 0 && j0 + 8 <= nact) {
-                vb = head_mask_bits(*reinterpret_cast<const uint2 *>(mask + gc + 8ll * c));
+                vb = M::full(mask, gc + 8ll * c, row, j0, nw);
                 if (vb) {
                     E::load8(logits, gc + 8ll * c, x);
                     head_fold<MODE>(a, x, vb, j0, key);
@@ -206,7 +238,7 @@ __global__ __launch_bounds__(64 * kHeadWaves) void k_head_fwd(const typename Hea
                 vb = 0;
                 for (int e = 0; e < 8; e++) {
                     const long long j = j0 + e;
-                    if (j < 0 || j >= nact || !mask[g0 + j]) continue;
+                    if (j < 0 || j >= nact || !M::one(mask, g0, row, j, nw)) continue;
                     vb |= 1u << e;
                     head_fold_one<MODE>(a, E::get(logits, g0 + j), j, key);
                 }
@@ -242,7 +274,7 @@ __global__ __launch_bounds__(64 * kHeadWaves) void k_head_fwd(const typename Hea
     float lp;
     if (MODE == ONGYM_HEAD_EVALUATE) {
         act = actions[row];
-        lp = (act >= 0 && act < nact && mask[g0 + act]) ? (E::get(logits, g0 + act) - a.m) - ls : -INFINITY;
+        lp = (act >= 0 && act < nact && M::one(mask, g0, row, act, nw)) ? (E::get(logits, g0 + act) - a.m) - ls : -INFINITY;
     } else {
         act = (any && a.idx < nact) ? a.idx : nact - 1;        // no valid finite entry (a caller error): reject, NaN
         lp = (E::get(logits, g0 + act) - a.m) - ls;
@@ -281,10 +313,7 @@ __global__ __launch_bounds__(64 * kHeadWaves) void k_head_bwd(const typename Hea
     for (int c = lane; c < nch; c += 64) {
         const long long j0 = 8ll * c - s0;
         if (j0 >= 0 && j0 + 8 <= nact) {
-            const int w = (int)(j0 >> 5), sh = (int)(j0 & 31);
-            uint64_t v = rb[w];
-            if (sh > 24) v |= (uint64_t)rb[w + 1] << 32;       // bits up to j0 + 7 < nact: word w + 1 exists
-            const uint32_t vb = (uint32_t)(v >> sh) & 0xFFu;
+            const uint32_t vb = head_bits8(rb, j0);
             float g[8];
             if (vb) {
                 float x[8];

@@ -4,6 +4,7 @@ observation + action mask -> masked policy in PyTorch-ROCm -> step(actions), eve
 (ongym_set_stream: no host synchronisation inside the loop).
 
     python tools/bench_rl.py [--gpus N] [--batch B] [--steps K] [--learner [--horizon H]]
+    python tools/bench_rl.py --ppo [--n-steps T] [--epochs E] [--minibatch R] [--torch-gae] [--steps ITERATIONS]
 
 Default: a masked random policy (env-side cost only).  `--learner`: a masked actor-critic MLP (368 -> 512 -> 512 -> 9601
 logits + value head, bf16 autocast) sampled every step through the library's masked categorical head
@@ -11,6 +12,11 @@ logits + value head, bf16 autocast) sampled every step through the library's mas
 the data flow of the reference's MaskablePPO scripts (examples/ONDM_2025/train_multi_masked_ppo.py:410-458: 14
 SubprocVecEnv workers feeding one learner; no PPO library is installed in this image).  The env writes into / reads from
 torch device tensors (`io_device=1`, torch.Tensor.data_ptr()); nothing crosses PCIe inside the loop.
+
+`--ppo`: MaskablePPO at the reference's hyperparameters (train_multi_masked_ppo.py:441-458): a T-step rollout keeps the packed
+action mask of every step (masked_categorical(..., mask_bits_out=bits[t])), rl.gae turns the step records into advantages
+(episode ends from `terminated`), and `--epochs` passes of shuffled `--minibatch`-row updates evaluate the stored actions
+through the packed-mask head.  `--steps` counts PPO iterations; the JSON line adds per-phase ms (device events) per iteration.
 
 `--gpus N`: one process per GPU (spawned as a child `python -m torch.distributed.run` before anything touches the GPU, or
 taken from the launcher's environment); rank k steps the global replicas shard_bounds(N*B, k, N) with request streams keyed
@@ -51,6 +57,11 @@ def main():
     ap.add_argument("--horizon", type=int, default=16)
     ap.add_argument("--torch-sampler", action="store_true", help="masked sampling with torch ops instead of ongym_sample_actions")
     ap.add_argument("--own-stream", action="store_true", help="round-2 behaviour: env on its own stream, three host syncs per step")
+    ap.add_argument("--ppo", action="store_true", help="MaskablePPO at the reference's hyperparameters; --steps counts PPO iterations")
+    ap.add_argument("--n-steps", type=int, default=32, help="--ppo: rollout length T")
+    ap.add_argument("--epochs", type=int, default=4, help="--ppo: update epochs per rollout")
+    ap.add_argument("--minibatch", type=int, default=32768, help="--ppo: rows per minibatch, shuffled across t and b")
+    ap.add_argument("--torch-gae", action="store_true", help="--ppo: GAE as a sequential torch loop instead of ongym_gae")
     args = ap.parse_args()
     if "RANK" not in os.environ and args.gpus > 1:
         raise SystemExit(spawn_ranks(args.gpus))
@@ -174,7 +185,107 @@ def main():
                 opt.step()
                 logps.clear(); values.clear(); rewards.clear()
 
-    for _ in range(5 if not args.learner else args.horizon):
+    if args.ppo:
+        # MaskablePPO (sb3-contrib, examples/ONDM_2025/train_multi_masked_ppo.py:441-458): GAE(0.99, 0.95), clip 0.2, entropy
+        # coefficient 0.03, value coefficient 0.5, gradient norm 0.5, Adam 3e-4, separate 512-256-128 tanh networks for pi and V
+        from optical_networking_gym.rl import gae
+        T, GAMMA, LAM, CLIP, ENT, VF, MAXNORM = args.n_steps, 0.99, 0.95, 0.2, 0.03, 0.5, 0.5
+        torch.manual_seed(0)
+
+        def mlp(n_out):
+            return torch.nn.Sequential(torch.nn.Linear(obs_dim, 512), torch.nn.Tanh(), torch.nn.Linear(512, 256), torch.nn.Tanh(),
+                                       torch.nn.Linear(256, 128), torch.nn.Tanh(), torch.nn.Linear(128, n_out)).to(dev)
+        pi_net, v_net = mlp(nact), mlp(1)
+        params = list(pi_net.parameters()) + list(v_net.parameters())
+        opt = torch.optim.Adam(params, lr=3e-4, eps=1e-5)
+        nw = (nact + 31) // 32
+        N = T * B
+        R = min(args.minibatch, N)
+        obs_t = torch.empty((T, B, obs_dim), dtype=torch.float32, device=dev)
+        bits_t = torch.empty((T, B, nw), dtype=torch.int32, device=dev)     # packed masks: 8x smaller than the bytes
+        acts_t = torch.empty((T, B), dtype=torch.int32, device=dev)
+        logp_t = torch.empty((T, B), dtype=torch.float32, device=dev)
+        vals_t = torch.empty((T, B), dtype=torch.float32, device=dev)
+        recs_t = torch.empty((T, B, nat.STEP_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        adv_t, ret_t = torch.empty((T, B), dtype=torch.float32, device=dev), torch.empty((T, B), dtype=torch.float32, device=dev)
+        obs_last = torch.empty((B, obs_dim), dtype=torch.float32, device=dev)
+        r_off, t_off = nat.STEP_DTYPE.fields["reward"][1], nat.STEP_DTYPE.fields["terminated"][1]
+        env._check(env.lib.ongym_observe(env._h, obs_last.data_ptr(), mask.data_ptr()), "observe")
+        ev = {k: [torch.cuda.Event(enable_timing=True) for _ in range(2)] for k in ("rollout", "gae", "update")}
+        phase_ms = {k: 0.0 for k in ev}
+        last_losses = {}
+
+        def rollout():
+            obs_t[0].copy_(obs_last)                    # the observation after the previous rollout's last step
+            for t in range(T):
+                with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
+                    logits, v = pi_net(obs_t[t]), v_net(obs_t[t]).float().squeeze(1)
+                a, lp, _ = masked_categorical(env, logits, mask, seed=7, mask_bits_out=bits_t[t])
+                acts_t[t].copy_(a); logp_t[t].copy_(lp); vals_t[t].copy_(v)
+                env._check(env.lib.ongym_step_actions(env._h, acts_t[t].data_ptr(), recs_t[t].data_ptr()), "step")
+                nxt = obs_t[t + 1] if t + 1 < T else obs_last
+                env._check(env.lib.ongym_observe(env._h, nxt.data_ptr(), mask.data_ptr()), "observe")
+            with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
+                return v_net(obs_last).float().squeeze(1)
+
+        def torch_gae(last_v):
+            # the sequential loop, cutting reward (f64) and terminated (u8) out of the 56-byte records step by step
+            a = torch.zeros(B, device=dev)
+            for t in reversed(range(T)):
+                rew = recs_t[t][:, r_off:r_off + 8].contiguous().view(torch.float64).squeeze(1).float()
+                nnt = 1.0 - recs_t[t][:, t_off].float()
+                vnext = last_v if t == T - 1 else vals_t[t + 1]
+                delta = rew + GAMMA * vnext * nnt - vals_t[t]
+                a = delta + GAMMA * LAM * nnt * a
+                adv_t[t].copy_(a)
+            torch.add(adv_t, vals_t, out=ret_t)
+
+        def update():
+            o_f, b_f, a_f = obs_t.view(N, obs_dim), bits_t.view(N, nw), acts_t.view(N)
+            lp_f, adv_f, ret_f = logp_t.view(N), adv_t.view(N), ret_t.view(N)
+            for _ in range(args.epochs):
+                perm = torch.randperm(N, device=dev)
+                for s0 in range(0, N, R):
+                    idx = perm[s0:s0 + R]
+                    adv = adv_f[idx]
+                    adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+                    with torch.autocast("cuda", dtype=torch.bfloat16):
+                        o = o_f[idx]
+                        logits, v = pi_net(o), v_net(o).float().squeeze(1)
+                    # evaluate the stored actions through the packed-mask, any-row-count head
+                    _, lp, ent = masked_categorical(env, logits, b_f[idx], a_f[idx])
+                    ratio = torch.exp(lp - lp_f[idx])
+                    pg = -torch.min(adv * ratio, adv * ratio.clamp(1 - CLIP, 1 + CLIP)).mean()
+                    vl = torch.nn.functional.mse_loss(ret_f[idx], v)
+                    el = -ent.mean()
+                    loss = pg + ENT * el + VF * vl
+                    opt.zero_grad(set_to_none=True)
+                    loss.backward()
+                    allreduce_mean_gradients(params, dist if not rehearse else None)     # ONE bucketed all-reduce (RCCL)
+                    torch.nn.utils.clip_grad_norm_(params, MAXNORM)
+                    opt.step()
+            last_losses.update(policy_loss=pg.detach(), value_loss=vl.detach(), entropy=-el.detach(), loss=loss.detach())
+
+        def rl_step(timed=True):   # noqa: F811  (one PPO iteration: T env-steps per replica)
+            ev["rollout"][0].record()
+            last_v = rollout()
+            ev["rollout"][1].record(); ev["gae"][0].record()
+            if args.torch_gae:
+                torch_gae(last_v)
+            else:
+                gae(env, recs_t, vals_t, last_v, GAMMA, LAM, out=(adv_t, ret_t))
+            ev["gae"][1].record(); ev["update"][0].record()
+            update()
+            ev["update"][1].record()
+            if timed:
+                torch.cuda.synchronize()
+                for k, (e0, e1) in ev.items():
+                    phase_ms[k] += e0.elapsed_time(e1)
+
+        rl_step(timed=False)                            # warm every shape of the timed window
+        p0 = torch.cat([p.detach().flatten().float() for p in params])
+
+    for _ in range(0 if args.ppo else 5 if not args.learner else args.horizon):
         rl_step()
 
     def fence():
@@ -189,20 +300,36 @@ def main():
         rl_step()
     fence()
     dt = time.perf_counter() - t0
-    acc = float(recs.cpu().numpy().view(nat.STEP_DTYPE)["accepted"].mean())
+    steps_per_iter = args.n_steps if args.ppo else 1              # env-steps per replica in one timed iteration
+    acc = float((recs_t[-1] if args.ppo else recs).cpu().numpy().view(nat.STEP_DTYPE)["accepted"].mean())
     import numpy as np
     _, dt_max, _ = reduce_run_statistics(np.zeros(1), dt, 0.0, dist, device=red_dev)
-    per_rank = gather_per_rank([B * args.steps / dt, acc], dist, device=red_dev)
+    per_rank = gather_per_rank([B * args.steps * steps_per_iter / dt, acc], dist, device=red_dev)
+    ppo = None
+    if args.ppo:
+        delta = (torch.cat([p.detach().flatten().float() for p in params]) - p0).norm().item()
+        ppo = {"phase_ms": {k: v / args.steps for k, v in phase_ms.items()},
+               "losses": {k: float(v) for k, v in last_losses.items()}, "param_delta": delta}
     if rank == 0:
         what = (f"observe + actor-critic MLP forward/sample + step, Adam update (gradients averaged over {world} rank(s)) every "
                 f"{args.horizon} steps" if args.learner else "observe + masked sampling in torch + step")
+        if args.ppo:
+            what = (f"MaskablePPO: {args.n_steps}-step rollout (pi/V MLPs, head sample with packed masks kept, step), "
+                    f"GAE ({'torch loop' if args.torch_gae else 'ongym_gae'}), {args.epochs} epoch(s) of minibatch updates "
+                    f"(packed-mask head evaluate), gradients averaged over {world} rank(s)")
         print(json.dumps({
             "metric": "RL env-steps/s (BASELINE config 5: learner loop consuming the vectorised QRMSA env)",
-            "value": B * world * args.steps / dt_max, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps,
-            "ms_per_step": dt_max / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "data": "synthetic",
+            "value": B * world * args.steps * steps_per_iter / dt_max, "unit": "env-steps/s", "n_gpus": world,
+            "steps": args.steps, "ms_per_step": dt_max / (args.steps * steps_per_iter) * 1e3, "higher_is_better": True,
+            "scaling": "weak", "data": "synthetic",
             "config": {"workload": f"QRMSA nsfnet320, gen_observation path: {what}", "batch_per_gpu": B,
                        "global_batch": B * world, "stream": "caller's (torch current stream)" if shared else "own + host syncs",
-                       "learner": bool(args.learner), "horizon": args.horizon if args.learner else None},
+                       "learner": bool(args.learner), "horizon": args.horizon if args.learner else None,
+                       "ppo": {"n_steps": args.n_steps, "epochs": args.epochs, "minibatch": min(args.minibatch, args.n_steps * B),
+                               "gamma": 0.99, "gae_lambda": 0.95, "clip": 0.2, "ent_coef": 0.03, "vf_coef": 0.5,
+                               "max_grad_norm": 0.5, "lr": 3e-4, "net_arch": [512, 256, 128],
+                               "gae": "torch" if args.torch_gae else "ongym_gae"} if args.ppo else None},
+            **(ppo or {}),
             "process_group": {"world_size": dist.get_world_size() if dist else 1, "backend": dist.get_backend() if dist else None,
                               "per_rank_value": [r[0] for r in per_rank], "per_rank_accepted": [r[1] for r in per_rank]},
             "rehearsal": rehearse or None}), flush=True)

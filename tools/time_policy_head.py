@@ -4,6 +4,10 @@ replaces (masked_fill(mask == 0, -1e8) + torch.distributions.Categorical, what s
 B = 16384 on the NSFNET-320 action mask of a loaded network (9601 actions), f32 and bf16 logits.
 
     python tools/time_policy_head.py [--batch B] [--iters N] [--head-only]
+    python tools/time_policy_head.py --packed [--rows R ...]     # bf16 evaluate + backward, packed bits vs bytes
+
+`--packed`: the PPO-update form (ongym_masked_categorical_rows / _backward_rows) at R = B and at the given row counts (default
+B and 262144: minibatch rows tiled from the B observed rows), byte mask vs packed bits, alternated over --reps rounds.
 
 Times are device events around N back-to-back calls after warm-up.  Bytes are algorithmic, from shapes: forward = logits +
 mask read + mask bits written; backward = logits + mask bits read + gradient written (per-row vectors not counted).
@@ -23,6 +27,9 @@ def main():
     ap.add_argument("--batch", type=int, default=16384)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--head-only", action="store_true", help="skip the torch formulation (profiler passes)")
+    ap.add_argument("--packed", action="store_true", help="bf16 evaluate + backward with packed bits vs bytes (only)")
+    ap.add_argument("--rows", type=int, nargs="*", default=None, help="--packed: row counts (default: B and 262144)")
+    ap.add_argument("--reps", type=int, default=3, help="--packed: alternated rounds")
     args = ap.parse_args()
     import torch
     import bench
@@ -69,6 +76,8 @@ def main():
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / args.iters
 
+    if args.packed:
+        return packed_vs_bytes(env, mask, args, timed, p)
     rows = []
     for dt, code in ((torch.bfloat16, nat.DTYPE_BF16), (torch.float32, nat.DTYPE_F32)):
         logits = (torch.randn((B, n), device=dev) * 2).to(dt)
@@ -126,6 +135,62 @@ def main():
         ratio = f"{r['ms'] / ref['ms']:9.1f}" if ref and r is not ref else ""
         print(f"{r['dtype']:5} {r['op']:9} {r['impl']:18} {r['ms']:8.3f} {extra} {ratio}")
     print(json.dumps(dict(batch=B, n_actions=n, valid_fraction=valid_frac, rows=rows)))
+
+
+def packed_vs_bytes(env, mask, args, timed, p):
+    """bf16 evaluate + backward through the _rows pair at R rows, the mask as bytes or packed bits, alternated"""
+    import torch
+    from optical_networking_gym import _native as nat
+    B, n = mask.shape
+    W = (n + 31) // 32
+    dev = mask.device
+    bits_b = torch.empty((B, W), dtype=torch.int32, device=dev)
+    lg = torch.randn((B, n), device=dev).to(torch.bfloat16)
+    a, lp, H, st = (torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, device=dev), torch.empty(B, device=dev),
+                    torch.empty((B, 2), device=dev))
+    env._check(env.lib.ongym_masked_categorical(env._h, p(lg), nat.DTYPE_BF16, p(mask), nat.HEAD_SAMPLE, 0, 0, p(a), p(lp), p(H),
+                                                p(st), p(bits_b)), "head")
+    res = []
+    for R in args.rows or (B, 262144):
+        reps = -(-R // B)
+        m_r, b_r = mask.repeat(reps, 1)[:R].contiguous(), bits_b.repeat(reps, 1)[:R].contiguous()
+        a_r = a.repeat(reps)[:R].contiguous()
+        logits = (torch.randn((R, n), device=dev) * 2).to(torch.bfloat16)
+        grad = torch.empty_like(logits)
+        lp, H, st = torch.empty(R, device=dev), torch.empty(R, device=dev), torch.empty((R, 2), device=dev)
+        g_lp, g_H = torch.randn(R, device=dev), torch.randn(R, device=dev)
+        keep = torch.empty((R, W), dtype=torch.int32, device=dev)       # bits the byte forward writes for its backward
+
+        def run(fmt):
+            m, bits_out = (m_r, keep) if fmt == nat.MASK_BYTES else (b_r, None)
+            saved = keep if fmt == nat.MASK_BYTES else b_r
+
+            def f():
+                env._check(env.lib.ongym_masked_categorical_rows(env._h, R, p(logits), nat.DTYPE_BF16, p(m), fmt, nat.HEAD_EVALUATE,
+                                                                 0, 0, p(a_r), p(lp), p(H), p(st),
+                                                                 None if bits_out is None else p(bits_out)), "rows")
+                env._check(env.lib.ongym_masked_categorical_backward_rows(env._h, R, p(logits), nat.DTYPE_BF16, p(saved), p(a_r),
+                                                                          p(st), p(H), p(g_lp), p(g_H), p(grad)), "bwd rows")
+            return f
+        ms = {nat.MASK_BYTES: [], nat.MASK_BITS: []}
+        for _ in range(args.reps):
+            for fmt in (nat.MASK_BYTES, nat.MASK_BITS):
+                ms[fmt].append(timed(run(fmt)))
+        for fmt, name in ((nat.MASK_BYTES, "bytes"), (nat.MASK_BITS, "bits")):
+            # evaluate reads logits + mask (+ writes bits for bytes); backward reads logits + bits, writes the gradient
+            mbytes = R * n if fmt == nat.MASK_BYTES else R * W * 4
+            nbytes = R * n * 2 + mbytes + (R * W * 4 if fmt == nat.MASK_BYTES else 0) + 2 * R * n * 2 + R * W * 4
+            res.append(dict(rows=R, mask=name, ms_min=min(ms[fmt]), ms_max=max(ms[fmt]), gbytes=nbytes / 1e9,
+                            tb_s=nbytes / min(ms[fmt]) / 1e9, mask_bytes_per_row=mbytes // R))
+        del logits, grad, m_r, b_r
+        torch.cuda.empty_cache()
+    print(f"bf16 evaluate + backward (ongym_masked_categorical_rows / _backward_rows), n_actions = {n}, byte mask vs packed bits, "
+          f"{args.reps} alternated rounds of {args.iters} calls (device events)")
+    print(f"{'rows':>7} {'mask':5} {'ms min':>8} {'ms max':>8} {'GB (alg.)':>10} {'TB/s':>6} {'mask B/row':>10}")
+    for r in res:
+        print(f"{r['rows']:7d} {r['mask']:5} {r['ms_min']:8.3f} {r['ms_max']:8.3f} {r['gbytes']:10.3f} {r['tb_s']:6.2f} "
+              f"{r['mask_bytes_per_row']:10d}")
+    print(json.dumps(dict(batch=B, n_actions=n, packed=res)))
 
 
 if __name__ == "__main__":
