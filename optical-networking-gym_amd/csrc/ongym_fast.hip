@@ -2,7 +2,7 @@
 //   hipcc -c -DONGYM_FAST_POLICY=<ONGYM_POLICY_* id> -DONGYM_FAST_WIDE=<0|1> ongym_fast.hip -o ongym_fast_p<id>[w].o
 // (WIDE = 0: every slot count of the configuration is <= 32, see ongym_env::fast_wide)
 // (the units compile in parallel; see __graft_entry__.build).  Each exports fast_launch / fast_occupancy / fast_prepare
-// for its policy; ongym_hip.hip dispatches on the policy id.
+// for its policy; ongym_hip.hip dispatches on the policy id (kLeanUnits).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,8 +18,9 @@ namespace ongym {
 
 constexpr int kPol = ONGYM_FAST_POLICY;
 
-// M64: link masks need two words (32 < n_links <= 52); ENT: interferers per lane cached in registers; WAVES: waves per
-// SIMD the register allocation is bounded for; POL: the policy (part of the kernel's name: one set of kernels per unit)
+// M64: link masks need two words (32 < n_links <= 32 + kM64HiBits = 41); ENT: interferers per lane cached in registers;
+// WAVES: waves per SIMD the register allocation is bounded for; POL: the policy (part of the kernel's name: one set of kernels
+// per unit)
 #ifndef ONGYM_FAST_WIDE
 #define ONGYM_FAST_WIDE 1
 #endif

@@ -35,11 +35,11 @@
 // The state in HBM is the generic kernels' (same arrays, same record codec), converted on load / store: every other entry
 // point keeps working on the same environment, and a launch may be split anywhere.
 //
-// Eligibility (checked on the host in build(), ongym_hip.hip; lean_policy() there decides per launch): policy-step mode,
+// Eligibility (checked on the host in build(), ongym_hip.hip; lean_unit() there decides per launch): policy-step mode,
 // device request generator or a host trace whose bit rates all come from the configured table, discrete bit rates (<= 8,
 // integer-valued), uniform attenuation, ase_shortcut, no defragmentation / disruptions / id tracking,
-// modulations_to_consider == n_mods, n_links <= 52, n_nodes <= 64, every slot count of the traffic table <= min(512,
-// tab_nmax), 2S+1 < 2048, and the policy's LDS block within 160 KiB.
+// modulations_to_consider == n_mods, n_links <= 32 + kM64HiBits = 41, n_nodes <= 64, every slot count of the traffic table
+// <= min(512, tab_nmax), 2S+1 < 2048, and the policy's LDS block within 160 KiB.
 #pragma once
 #include "ongym_device.hpp"
 
@@ -50,7 +50,7 @@ constexpr int kNearHalfSlots = 32;   // candidate-lane evaluation: interferers t
 
 // ---- path record (8 dwords, 32-byte aligned: one s_load_dwordx8) -------------------------------------------------------
 struct PathRec {
-    uint32_t hops, mask_lo, mask_hi, id;   // mask = links of the path (bit l = link l), n_links <= 52
+    uint32_t hops, mask_lo, mask_hi, id;   // mask = links of the path (bit l = link l), n_links <= 41
     double ase, w1;                        // path_ase[id], path_w1[id]
 };
 static_assert(sizeof(PathRec) == 32, "PathRec must be 32 bytes");

@@ -8,6 +8,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include <map>
@@ -160,7 +161,7 @@ __global__ __launch_bounds__(64, ONGYM_OBS_WAVES) void k_observe(const Params *_
     STAMPW(c, 0);
     const size_t obs_dim = 3 + P.k_paths + (size_t)P.k_paths * P.n_mods_consider * 12;
     const size_t nact = (size_t)P.k_paths * P.n_mods_consider * P.n_slots + 1;
-    const ObsLayout lay = obs_layout(P);          // observe_lds on the host sizes the block with the same function
+    const ObsLayout lay = obs_layout(P);          // ongym_observe sizes the block with the same function
     double *Fx = reinterpret_cast<double *>(smem + lay.fx);
     uint16_t *xlist = reinterpret_cast<uint16_t *>(smem + lay.xlist);
     uint64_t *Vw = reinterpret_cast<uint64_t *>(smem + lay.vw);
@@ -375,6 +376,95 @@ hipError_t raise_lds_limit(int device, const void *kernel, size_t bytes) {
     const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e == hipSuccess) cur = bytes;
     return e;
+}
+
+// Every launch of a kernel with dynamic LDS: the kernel's limit is raised first (a no-op up to the default 64 KiB), then it runs
+// with one wavefront per workgroup.
+template <class... KArgs, class... Args>
+static int launch_lds(ongym_env *env, void (*kernel)(KArgs...), dim3 grid, size_t lds, Args... args) {
+    HIP_TRY(env, raise_lds_limit(env->cfg.device, reinterpret_cast<const void *>(kernel), lds));
+    hipLaunchKernelGGL(kernel, grid, dim3(64), lds, env->stream, args...);
+    HIP_TRY(env, hipGetLastError());
+    return 0;
+}
+
+// A runtime value as a compile-time constant: f(std::integral_constant<T, V>) for the V of Vs equal to v (the last V if none
+// is; callers validate v first).  Each V instantiates f once.
+template <class T, T V, T... Vs, class F>
+static auto dispatch(T v, F &&f) {
+    if constexpr (sizeof...(Vs) > 0)
+        if (v != V) return dispatch<T, Vs...>(v, f);
+    return f(std::integral_constant<T, V>{});
+}
+
+// f(UA, R32): the state layout of the environment (uniform attenuation, 32-bit service records) as template arguments
+template <class F>
+static auto with_layout(const Params &P, F &&f) {
+    return dispatch<bool, true, false>(P.uniform_alpha != 0, [&](auto UA) {
+        return dispatch<bool, true, false>(P.rec32 != 0, [&](auto R32) { return f(UA, R32); });
+    });
+}
+
+// The lean units (ongym_fast.hip): the policies that have one, each with its narrow and its wide build.  build() prepares them
+// in this order; without the first row (first fit) no lean kernel runs.
+struct LeanFns {
+    int (*prepare)(ongym_env *);
+    int (*launch)(ongym_env *, int, ongym_step_rec *);
+    int (*occupancy)(ongym_env *, int *, int *);
+};
+static const struct { int policy; LeanFns narrow, wide; } kLeanUnits[] = {
+    {ONGYM_POLICY_FIRST_FIT, {fast_prepare_p0, fast_launch_p0, fast_occupancy_p0},
+     {fast_prepare_p0w, fast_launch_p0w, fast_occupancy_p0w}},
+    {ONGYM_POLICY_LOAD_BALANCING, {fast_prepare_p1, fast_launch_p1, fast_occupancy_p1},
+     {fast_prepare_p1w, fast_launch_p1w, fast_occupancy_p1w}},
+    {ONGYM_POLICY_HIGHEST_SNR, {fast_prepare_p2, fast_launch_p2, fast_occupancy_p2},
+     {fast_prepare_p2w, fast_launch_p2w, fast_occupancy_p2w}},
+    {ONGYM_POLICY_LOWEST_FRAGMENTATION, {fast_prepare_p10, fast_launch_p10, fast_occupancy_p10},
+     {fast_prepare_p10w, fast_launch_p10w, fast_occupancy_p10w}},
+};
+
+// The lean unit (narrow or wide build) ongym_step_policy(policy) runs, or nullptr: the generic kernel runs.
+static const LeanFns *lean_unit(const ongym_env *env, int policy) {
+    if (!env->fast_ok || env->trace_used) return nullptr;
+    if (!(env->P.req_mode == kReqRng || (env->P.req_mode == kReqTrace && env->trace_fast_ok))) return nullptr;
+    for (const auto &u : kLeanUnits)
+        if (u.policy == policy && (env->lean_policies >> policy & 1u)) return env->fast_wide ? &u.wide : &u.narrow;
+    return nullptr;
+}
+
+// k_run's POLICY template argument: own instantiations for first fit, load balancing and highest SNR, one shared by the scored
+// policies (ongym_scored.hpp) and one by the other ids
+static int run_class(int policy) {
+    if (policy == ONGYM_POLICY_HIGHEST_SNR || policy == ONGYM_POLICY_LOAD_BALANCING) return policy;
+    if (policy >= ONGYM_POLICY_LOWEST_FRAGMENTATION) return kPolicyScored;
+    return policy >= ONGYM_POLICY_LOWEST_SPECTRUM ? kPolicyMisc : ONGYM_POLICY_FIRST_FIT;
+}
+
+// k_run's dynamic LDS: the state block, plus the field of highest SNR (Fx, Vw, xlist, needx) or the capacity-loss scratch of
+// MSCL (scored_lds_bytes; lowest fragmentation needs none)
+static size_t run_lds(const ongym_env *env, int policy) {
+    const Params &P = env->P;
+    if (policy == ONGYM_POLICY_HIGHEST_SNR)
+        return ((env->lds + ((size_t)2 * P.n_slots + 2) * (sizeof(double) + 2 + 1) + kMaxMods * kMaxRowWords * 8) + 15) & ~(size_t)15;
+    if (policy == ONGYM_POLICY_MSCL) return ((env->lds + 15) & ~(size_t)15) + scored_lds_bytes(P.row_words);
+    return env->lds;
+}
+
+// f(kernel, dynamic LDS bytes) of the generic step kernel that runs `policy` on this environment (action steps: first fit)
+template <class F>
+static int with_run_kernel(const ongym_env *env, int policy, F &&f) {
+    const Params &P = env->P;
+    const size_t lds = run_lds(env, policy);
+    return dispatch<int, ONGYM_POLICY_HIGHEST_SNR, ONGYM_POLICY_LOAD_BALANCING, kPolicyScored, kPolicyMisc, ONGYM_POLICY_FIRST_FIT>(
+        run_class(policy), [&](auto POL) {
+            if (P.track_ids)   // defragmentation / service-id tracking (uniform attenuation, checked at create)
+                return dispatch<bool, true, false>(P.rec32 != 0, [&](auto R32) { return f(k_run<true, R32, 4, POL, true>, lds); });
+            return with_layout(P, [&](auto UA, auto R32) {
+                if constexpr (POL == ONGYM_POLICY_FIRST_FIT)   // 5 waves per SIMD when the state block is <= 8 KiB
+                    if (env->lds <= 8192) return f(k_run<UA, R32, 5, POL>, lds);
+                return f(k_run<UA, R32, 4, POL>, lds);
+            });
+        });
 }
 
 static int push_params(ongym_env *env) {
@@ -635,7 +725,7 @@ static int build(ongym_env *env, const ongym_config *c) {
     {
         bool ok = uniform && P.ase_shortcut && !P.track_ids && !P.measure_disruptions && c->bit_rate_mode == 0 &&
                   P.n_mods_consider == M &&
-                  c->n_bit_rates <= 8 && E <= 52 && N <= 64 && P.pair_tab2k != nullptr;
+                  c->n_bit_rates <= 8 && E <= 32 + (int)kM64HiBits && N <= 64 && P.pair_tab2k != nullptr;
         const char *force = std::getenv("ONGYM_FORCE_GENERIC");
         if (force && force[0] == '1') ok = false;
         int max_n = 0;
@@ -652,8 +742,7 @@ static int build(ongym_env *env, const ongym_config *c) {
         if (flds > 160 * 1024) ok = false;
         P.path_hash_keys = nullptr; P.path_hash_vals = nullptr; P.path_hash_bits = 0; P.pad_hash = 0;
         if (ok && m64) {
-            // the M64 record keeps the link set (<= 41 bits) instead of the path id: it must identify the route
-            if (E > 32 + (int)kM64HiBits) ok = false;
+            // the M64 record keeps the link set (<= 32 + kM64HiBits bits) instead of the path id: it must identify the route
             int bits = 4;
             while ((1 << bits) < 4 * NP) bits++;
             std::vector<uint64_t> keys((size_t)1 << bits, ~0ull);
@@ -728,34 +817,13 @@ static int build(ongym_env *env, const ongym_config *c) {
         for (size_t i = 0; i < all.size(); i++) all[i] = row[i % P.row_words];
         HIP_TRY(env, hipMemcpy(P.occ, all.data(), all.size() * 8, hipMemcpyHostToDevice));
     }
-    env->lds = lds_bytes(P);
-    if (env->lds > 64 * 1024) {
-        if (env->lds > 160 * 1024) return fail_arg(env, "state does not fit the 160 KiB LDS: lower capacity", ONGYM_E_LIMIT);
-#define ONGYM_SET_LDS(K) HIP_TRY(env, raise_lds_limit(env->cfg.device, reinterpret_cast<const void *>(&K), env->lds))
-        ONGYM_SET_LDS((k_run<true, true, 4, 0>)); ONGYM_SET_LDS((k_run<true, false, 4, 0>));
-        ONGYM_SET_LDS((k_run<false, true, 4, 0>)); ONGYM_SET_LDS((k_run<false, false, 4, 0>));
-        ONGYM_SET_LDS((k_run<true, true, 4, 1>)); ONGYM_SET_LDS((k_run<true, false, 4, 1>));
-        ONGYM_SET_LDS((k_run<false, true, 4, 1>)); ONGYM_SET_LDS((k_run<false, false, 4, 1>));
-        ONGYM_SET_LDS((k_run<true, true, 4, kPolicyMisc>)); ONGYM_SET_LDS((k_run<true, false, 4, kPolicyMisc>));
-        ONGYM_SET_LDS((k_run<false, true, 4, kPolicyMisc>)); ONGYM_SET_LDS((k_run<false, false, 4, kPolicyMisc>));
-        if (P.track_ids) {
-            ONGYM_SET_LDS((k_run<true, true, 4, 0, true>)); ONGYM_SET_LDS((k_run<true, false, 4, 0, true>));
-            ONGYM_SET_LDS((k_run<true, true, 4, 1, true>)); ONGYM_SET_LDS((k_run<true, false, 4, 1, true>));
-            ONGYM_SET_LDS((k_run<true, true, 4, kPolicyMisc, true>)); ONGYM_SET_LDS((k_run<true, false, 4, kPolicyMisc, true>));
+    env->lds = lds_bytes(P);   // the launches raise their kernel's LDS limit above 64 KiB (launch_lds)
+    if (env->lds > 160 * 1024) return fail_arg(env, "state does not fit the 160 KiB LDS: lower capacity", ONGYM_E_LIMIT);
+    if (env->fast_ok) {   // the lean units: LDS limits; a policy whose block does not fit the CU keeps the generic kernel
+        for (const auto &u : kLeanUnits) {
+            if (env->fast_ok && (env->fast_wide ? u.wide : u.narrow).prepare(env) == 0) env->lean_policies |= 1u << u.policy;
+            else if (u.policy == ONGYM_POLICY_FIRST_FIT) env->fast_ok = false;
         }
-        ONGYM_SET_LDS((k_query<true, true>)); ONGYM_SET_LDS((k_query<true, false>));
-        ONGYM_SET_LDS((k_query<false, true>)); ONGYM_SET_LDS((k_query<false, false>));
-        ONGYM_SET_LDS((k_query_gsnr_many<true, true>)); ONGYM_SET_LDS((k_query_gsnr_many<true, false>));
-        ONGYM_SET_LDS((k_query_gsnr_many<false, true>)); ONGYM_SET_LDS((k_query_gsnr_many<false, false>));
-        ONGYM_SET_LDS(k_reset);
-#undef ONGYM_SET_LDS
-    }
-    if (env->fast_ok) {   // the lean kernels of every policy that has one (ongym_fast.hip): LDS limits; a policy whose block
-                          // does not fit the CU keeps the generic kernel
-        if (ONGYM_FAST_CALL(fast_prepare, 0, env)) env->fast_ok = false;
-        env->fast_lb_ok = env->fast_ok && ONGYM_FAST_CALL(fast_prepare, 1, env) == 0;
-        env->fast_hsnr_ok = env->fast_ok && ONGYM_FAST_CALL(fast_prepare, 2, env) == 0;
-        env->fast_lf_ok = env->fast_ok && ONGYM_FAST_CALL(fast_prepare, 10, env) == 0;
         env->err.clear();
     }
     // scratch for queries / host-buffer I/O
@@ -841,18 +909,6 @@ void ongym_destroy(ongym_env *env) {
 
 /* Resident workgroups (= replicas = wavefronts) per compute unit of the kernel that ongym_step_policy(first fit) launches,
  * as the HIP occupancy query reports it for this environment's LDS size. Diagnostic. */
-static bool lean_policy(const ongym_env *env, int policy) {      // does ongym_step_policy(policy) run a lean kernel?
-    if (!env->fast_ok || env->trace_used) return false;
-    if (!(env->P.req_mode == kReqRng || (env->P.req_mode == kReqTrace && env->trace_fast_ok))) return false;
-    switch (policy) {
-        case ONGYM_POLICY_FIRST_FIT: return true;
-        case ONGYM_POLICY_LOAD_BALANCING: return env->fast_lb_ok;
-        case ONGYM_POLICY_HIGHEST_SNR: return env->fast_hsnr_ok;
-        case ONGYM_POLICY_LOWEST_FRAGMENTATION: return env->fast_lf_ok;
-        default: return false;
-    }
-}
-
 int ongym_query_occupancy(ongym_env *env, int32_t *blocks_per_cu, int32_t *lds_bytes, int32_t *lean_kernel) {
     return ongym_query_occupancy_policy(env, ONGYM_POLICY_FIRST_FIT, blocks_per_cu, lds_bytes, lean_kernel);
 }
@@ -862,16 +918,9 @@ int ongym_query_occupancy_policy(ongym_env *env, int32_t policy, int32_t *blocks
     if (policy < ONGYM_POLICY_FIRST_FIT || policy >= ONGYM_POLICY_COUNT) return fail_arg(env, "unknown policy id");
     HIP_TRY(env, hipSetDevice(env->cfg.device));
     int nb = 0, lds = 0;
-    const bool lean = lean_policy(env, policy);
+    const LeanFns *lean = lean_unit(env, policy);
     if (lean) {
-        int rc;
-        switch (policy) {
-            case ONGYM_POLICY_LOAD_BALANCING: rc = ONGYM_FAST_CALL(fast_occupancy, 1, env, &nb, &lds); break;
-            case ONGYM_POLICY_HIGHEST_SNR: rc = ONGYM_FAST_CALL(fast_occupancy, 2, env, &nb, &lds); break;
-            case ONGYM_POLICY_LOWEST_FRAGMENTATION: rc = ONGYM_FAST_CALL(fast_occupancy, 10, env, &nb, &lds); break;
-            default: rc = ONGYM_FAST_CALL(fast_occupancy, 0, env, &nb, &lds); break;
-        }
-        if (rc) return rc;
+        if (int rc = lean->occupancy(env, &nb, &lds)) return rc;
         *lds_bytes = lds;
     } else {
         // the generic kernel's state block (the policies with scratch ask for more at launch time)
@@ -978,9 +1027,7 @@ int ongym_reset(ongym_env *env, const uint8_t *mask) {
             dmask = env->d_mask;
         }
     }
-    hipLaunchKernelGGL(k_reset, dim3(env->P.batch), dim3(64), env->lds, env->stream, env->d_P, dmask);
-    HIP_TRY(env, hipGetLastError());
-    return ONGYM_OK;
+    return launch_lds(env, k_reset, dim3(env->P.batch), env->lds, env->d_P, dmask);
 }
 
 int ongym_reset_episode_counters(ongym_env *env, const uint8_t *mask) {
@@ -1005,103 +1052,16 @@ int ongym_reset_episode_counters(ongym_env *env, const uint8_t *mask) {
     return ONGYM_OK;
 }
 
-static size_t observe_lds(const ongym_env *env) { return obs_layout(env->P).total; }   // k_observe's block (ongym_device.hpp)
-
-static size_t field_lds(const ongym_env *env) {   // k_observe / highest-SNR k_run: state block + Fx, Vw, xlist, needx
-    const Params &P = env->P;
-    return ((env->lds + ((size_t)2 * P.n_slots + 2) * (sizeof(double) + 2 + 1) + kMaxMods * kMaxRowWords * 8) + 15) & ~(size_t)15;
-}
-
-// lowest fragmentation needs no scratch; MSCL the block of scored_lds_bytes
-static size_t scored_lds(const ongym_env *env, int policy) {
-    return policy == ONGYM_POLICY_MSCL ? ((env->lds + 15) & ~(size_t)15) + scored_lds_bytes(env->P.row_words) : env->lds;
-}
-
 static int launch_run(ongym_env *env, int mode, int policy, int nsteps, const int32_t *d_actions, int32_t *d_act_out,
                       uint8_t *d_flag_out, ongym_step_rec *d_out) {
     HIP_TRY(env, hipEventRecord(env->ev0, env->stream));
-    const dim3 grid(env->P.batch), block(64);
-    if (mode == kModePolicyStep && lean_policy(env, policy)) {
-        // the lean kernels: same results, half the issued instructions (ongym_fast.hpp)
-        int rc;
-        switch (policy) {
-            case ONGYM_POLICY_LOAD_BALANCING: rc = ONGYM_FAST_CALL(fast_launch, 1, env, nsteps, d_out); break;
-            case ONGYM_POLICY_HIGHEST_SNR: rc = ONGYM_FAST_CALL(fast_launch, 2, env, nsteps, d_out); break;
-            case ONGYM_POLICY_LOWEST_FRAGMENTATION: rc = ONGYM_FAST_CALL(fast_launch, 10, env, nsteps, d_out); break;
-            default: rc = ONGYM_FAST_CALL(fast_launch, 0, env, nsteps, d_out); break;
-        }
-        if (rc) return rc;
-        HIP_TRY(env, hipEventRecord(env->ev1, env->stream));
-        env->timed = true;
-        return 0;
-    }
-    if (policy == ONGYM_POLICY_HIGHEST_SNR && field_lds(env) > 64 * 1024) {
-        HIP_TRY(env, raise_lds_limit(env->cfg.device, reinterpret_cast<const void *>(&k_run<true, true, 4, ONGYM_POLICY_HIGHEST_SNR>), field_lds(env)));
-        HIP_TRY(env, raise_lds_limit(env->cfg.device, reinterpret_cast<const void *>(&k_run<true, false, 4, ONGYM_POLICY_HIGHEST_SNR>), field_lds(env)));
-        HIP_TRY(env, raise_lds_limit(env->cfg.device, reinterpret_cast<const void *>(&k_run<false, true, 4, ONGYM_POLICY_HIGHEST_SNR>), field_lds(env)));
-        HIP_TRY(env, raise_lds_limit(env->cfg.device, reinterpret_cast<const void *>(&k_run<false, false, 4, ONGYM_POLICY_HIGHEST_SNR>), field_lds(env)));
-    }
-#define ONGYM_LAUNCH_DEFRAG(R, POL, LDS)                                                                           \
-    hipLaunchKernelGGL((k_run<true, R, 4, POL, true>), grid, block, LDS, env->stream, env->d_P, mode, nsteps,      \
-                       d_actions, d_act_out, d_flag_out, d_out, policy)
-    if (env->P.track_ids) {   // defragmentation / service-id tracking (uniform attenuation, checked at create): own instantiations
-        if (policy == ONGYM_POLICY_HIGHEST_SNR) {
-            if (field_lds(env) > 64 * 1024) {
-                HIP_TRY(env, raise_lds_limit(env->cfg.device, reinterpret_cast<const void *>(&k_run<true, true, 4, ONGYM_POLICY_HIGHEST_SNR, true>), field_lds(env)));
-                HIP_TRY(env, raise_lds_limit(env->cfg.device, reinterpret_cast<const void *>(&k_run<true, false, 4, ONGYM_POLICY_HIGHEST_SNR, true>), field_lds(env)));
-            }
-            if (env->P.rec32) ONGYM_LAUNCH_DEFRAG(true, ONGYM_POLICY_HIGHEST_SNR, field_lds(env));
-            else ONGYM_LAUNCH_DEFRAG(false, ONGYM_POLICY_HIGHEST_SNR, field_lds(env));
-        } else if (policy == ONGYM_POLICY_LOAD_BALANCING) {
-            if (env->P.rec32) ONGYM_LAUNCH_DEFRAG(true, ONGYM_POLICY_LOAD_BALANCING, env->lds);
-            else ONGYM_LAUNCH_DEFRAG(false, ONGYM_POLICY_LOAD_BALANCING, env->lds);
-        } else if (policy >= ONGYM_POLICY_LOWEST_FRAGMENTATION) {
-            if (scored_lds(env, policy) > 64 * 1024) {
-                HIP_TRY(env, raise_lds_limit(env->cfg.device, reinterpret_cast<const void *>(&k_run<true, true, 4, kPolicyScored, true>), scored_lds(env, policy)));
-                HIP_TRY(env, raise_lds_limit(env->cfg.device, reinterpret_cast<const void *>(&k_run<true, false, 4, kPolicyScored, true>), scored_lds(env, policy)));
-            }
-            if (env->P.rec32) ONGYM_LAUNCH_DEFRAG(true, kPolicyScored, scored_lds(env, policy));
-            else ONGYM_LAUNCH_DEFRAG(false, kPolicyScored, scored_lds(env, policy));
-        } else if (policy >= ONGYM_POLICY_LOWEST_SPECTRUM) {
-            if (env->P.rec32) ONGYM_LAUNCH_DEFRAG(true, kPolicyMisc, env->lds);
-            else ONGYM_LAUNCH_DEFRAG(false, kPolicyMisc, env->lds);
-        } else {
-            if (env->P.rec32) ONGYM_LAUNCH_DEFRAG(true, ONGYM_POLICY_FIRST_FIT, env->lds);
-            else ONGYM_LAUNCH_DEFRAG(false, ONGYM_POLICY_FIRST_FIT, env->lds);
-        }
-        HIP_TRY(env, hipGetLastError());
-        HIP_TRY(env, hipEventRecord(env->ev1, env->stream));
-        env->timed = true;
-        return 0;
-    }
-#undef ONGYM_LAUNCH_DEFRAG
-#define ONGYM_LAUNCH_RUN(UA, R)                                                                                    \
-    do {                                                                                                           \
-        if (policy == ONGYM_POLICY_HIGHEST_SNR)                                                                    \
-            hipLaunchKernelGGL((k_run<UA, R, 4, ONGYM_POLICY_HIGHEST_SNR>), grid, block, field_lds(env),            \
-                               env->stream, env->d_P, mode, nsteps, d_actions, d_act_out, d_flag_out, d_out, policy);      \
-        else if (policy == ONGYM_POLICY_LOAD_BALANCING)                                                            \
-            hipLaunchKernelGGL((k_run<UA, R, 4, ONGYM_POLICY_LOAD_BALANCING>), grid, block, env->lds, env->stream,  \
-                               env->d_P, mode, nsteps, d_actions, d_act_out, d_flag_out, d_out, policy);                   \
-        else if (policy >= ONGYM_POLICY_LOWEST_FRAGMENTATION) {                                                    \
-            if (scored_lds(env, policy) > 64 * 1024)                                                                       \
-                HIP_TRY(env, raise_lds_limit(env->cfg.device, reinterpret_cast<const void *>(&k_run<UA, R, 4, kPolicyScored>), scored_lds(env, policy))); \
-            hipLaunchKernelGGL((k_run<UA, R, 4, kPolicyScored>), grid, block, scored_lds(env, policy), env->stream,         \
-                               env->d_P, mode, nsteps, d_actions, d_act_out, d_flag_out, d_out, policy);                   \
-        } else if (policy >= ONGYM_POLICY_LOWEST_SPECTRUM)                                                         \
-            hipLaunchKernelGGL((k_run<UA, R, 4, kPolicyMisc>), grid, block, env->lds, env->stream,                  \
-                               env->d_P, mode, nsteps, d_actions, d_act_out, d_flag_out, d_out, policy);                   \
-        else if (env->lds <= 8192)                                                                                 \
-            hipLaunchKernelGGL((k_run<UA, R, 5, ONGYM_POLICY_FIRST_FIT>), grid, block, env->lds, env->stream,       \
-                               env->d_P, mode, nsteps, d_actions, d_act_out, d_flag_out, d_out, policy);                   \
-        else                                                                                                       \
-            hipLaunchKernelGGL((k_run<UA, R, 4, ONGYM_POLICY_FIRST_FIT>), grid, block, env->lds, env->stream,       \
-                               env->d_P, mode, nsteps, d_actions, d_act_out, d_flag_out, d_out, policy);                   \
-    } while (0)
-    if (env->P.uniform_alpha) { if (env->P.rec32) ONGYM_LAUNCH_RUN(true, true); else ONGYM_LAUNCH_RUN(true, false); }
-    else { if (env->P.rec32) ONGYM_LAUNCH_RUN(false, true); else ONGYM_LAUNCH_RUN(false, false); }
-#undef ONGYM_LAUNCH_RUN
-    HIP_TRY(env, hipGetLastError());
+    // the lean kernels: same results, half the issued instructions (ongym_fast.hpp)
+    const LeanFns *lean = mode == kModePolicyStep ? lean_unit(env, policy) : nullptr;
+    const int rc = lean ? lean->launch(env, nsteps, d_out) : with_run_kernel(env, policy, [&](auto kernel, size_t lds) {
+        return launch_lds(env, kernel, dim3(env->P.batch), lds, env->d_P, mode, nsteps, d_actions, d_act_out, d_flag_out, d_out,
+                          policy);
+    });
+    if (rc) return rc;
     HIP_TRY(env, hipEventRecord(env->ev1, env->stream));
     env->timed = true;
     return 0;
@@ -1115,8 +1075,7 @@ static int ensure_out(ongym_env *env, size_t n) {
     return 0;
 }
 
-int ongym_step_policy(ongym_env *env, int32_t policy, int32_t nsteps, ongym_step_rec *out) {
-    if (!env) return ONGYM_E_ARG;
+static int check_policy(ongym_env *env, int32_t policy) {
     if (policy < ONGYM_POLICY_FIRST_FIT || policy >= ONGYM_POLICY_COUNT) return fail_arg(env, "unknown policy id");
     if (policy >= ONGYM_POLICY_LOWEST_SPECTRUM && env->P.k_paths > 8)
         return fail_arg(env, "this policy supports at most 8 candidate routes", ONGYM_E_LIMIT);
@@ -1124,10 +1083,16 @@ int ongym_step_policy(ongym_env *env, int32_t policy, int32_t nsteps, ongym_step
         return fail_arg(env, "only the first-fit policy is fused for modulations_to_consider < n_mods", ONGYM_E_LIMIT);
     if (policy == ONGYM_POLICY_MSCL && (env->P.bit_rate_mode != 0 || env->P.n_bit_rates <= 0))
         return fail_arg(env, "the MSCL policy sums its capacity loss over the discrete bit rates: bit_rate_mode must be discrete", ONGYM_E_LIMIT);
+    return 0;
+}
+
+int ongym_step_policy(ongym_env *env, int32_t policy, int32_t nsteps, ongym_step_rec *out) {
+    if (!env) return ONGYM_E_ARG;
+    int rc;
+    if ((rc = check_policy(env, policy))) return rc;
     if (nsteps <= 0) return fail_arg(env, "nsteps must be positive");
     if (!env->has_source) { env->err = "no request source: call ongym_seed or ongym_set_requests first"; return ONGYM_E_STATE; }
     HIP_TRY(env, hipSetDevice(env->cfg.device));
-    int rc;
     if (out && !env->cfg.io_device) {
         size_t n = (size_t)nsteps * env->P.batch;
         if ((rc = ensure_out(env, n))) return rc;
@@ -1153,17 +1118,6 @@ int ongym_step_actions(ongym_env *env, const int32_t *actions, ongym_step_rec *o
     } else if ((rc = launch_run(env, kModeActionStep, ONGYM_POLICY_FIRST_FIT, 1, env->d_actions, nullptr, nullptr, nullptr))) return rc;
     HIP_TRY(env, hipStreamSynchronize(env->stream));
     return ONGYM_OK;
-}
-
-static int check_policy(ongym_env *env, int32_t policy) {
-    if (policy < ONGYM_POLICY_FIRST_FIT || policy >= ONGYM_POLICY_COUNT) return fail_arg(env, "unknown policy id");
-    if (policy >= ONGYM_POLICY_LOWEST_SPECTRUM && env->P.k_paths > 8)
-        return fail_arg(env, "this policy supports at most 8 candidate routes", ONGYM_E_LIMIT);
-    if (policy != ONGYM_POLICY_FIRST_FIT && env->P.n_mods_consider < env->P.n_mods)
-        return fail_arg(env, "only the first-fit policy is fused for modulations_to_consider < n_mods", ONGYM_E_LIMIT);
-    if (policy == ONGYM_POLICY_MSCL && (env->P.bit_rate_mode != 0 || env->P.n_bit_rates <= 0))
-        return fail_arg(env, "the MSCL policy sums its capacity loss over the discrete bit rates: bit_rate_mode must be discrete", ONGYM_E_LIMIT);
-    return 0;
 }
 
 int ongym_step_actions_bundle(ongym_env *env, const int32_t *actions, int32_t next_policy, ongym_step_rec *rec_out,
@@ -1235,13 +1189,6 @@ int ongym_observe(ongym_env *env, float *obs, uint8_t *mask) {
     const size_t obs_dim = 3 + P.k_paths + (size_t)P.k_paths * P.n_mods_consider * 12;
     const size_t nact = (size_t)P.k_paths * P.n_mods_consider * P.n_slots + 1;
     const size_t B = (size_t)P.batch;
-    const size_t lds = observe_lds(env);
-    if (lds > 64 * 1024) {
-        HIP_TRY(env, raise_lds_limit(env->cfg.device, reinterpret_cast<const void *>(&k_observe<true, true>), lds));
-        HIP_TRY(env, raise_lds_limit(env->cfg.device, reinterpret_cast<const void *>(&k_observe<true, false>), lds));
-        HIP_TRY(env, raise_lds_limit(env->cfg.device, reinterpret_cast<const void *>(&k_observe<false, true>), lds));
-        HIP_TRY(env, raise_lds_limit(env->cfg.device, reinterpret_cast<const void *>(&k_observe<false, false>), lds));
-    }
     float *d_obs = obs; uint8_t *d_mask = mask;
     if (!env->cfg.io_device) {
         if (!env->d_obs) {
@@ -1254,11 +1201,10 @@ int ongym_observe(ongym_env *env, float *obs, uint8_t *mask) {
     }
     HIP_TRY(env, hipMemsetAsync(d_mask, 0, B * nact, env->stream));     // k_observe only sets the ones
     HIP_TRY(env, hipEventRecord(env->ev0, env->stream));
-#define ONGYM_LAUNCH_OBS(UA, R) hipLaunchKernelGGL((k_observe<UA, R>), dim3(P.batch), dim3(64), lds, env->stream, env->d_P, d_obs, d_mask)
-    if (P.uniform_alpha) { if (P.rec32) ONGYM_LAUNCH_OBS(true, true); else ONGYM_LAUNCH_OBS(true, false); }
-    else { if (P.rec32) ONGYM_LAUNCH_OBS(false, true); else ONGYM_LAUNCH_OBS(false, false); }
-#undef ONGYM_LAUNCH_OBS
-    HIP_TRY(env, hipGetLastError());
+    const int rc = with_layout(P, [&](auto UA, auto R32) {
+        return launch_lds(env, k_observe<UA, R32>, dim3(P.batch), obs_layout(P).total, env->d_P, d_obs, d_mask);
+    });
+    if (rc) return rc;
     HIP_TRY(env, hipEventRecord(env->ev1, env->stream));
     env->timed = true;
     if (!env->cfg.io_device) {
@@ -1322,23 +1268,16 @@ int ongym_masked_categorical_rows(ongym_env *env, int32_t rows, const void *logi
     HIP_TRY(env, hipSetDevice(env->cfg.device));
     const dim3 grid((rows + kHeadWaves - 1) / kHeadWaves), block(64 * kHeadWaves);
     const size_t shm = mask_bits ? lds : 0;
-#define ONGYM_HEAD_FWD(DT, MODE, MF)                                                                                       \
-    hipLaunchKernelGGL((k_head_fwd<DT, MODE, MF>), grid, block, shm, env->stream,                                          \
-                       static_cast<const HeadElem<DT>::T *>(logits), static_cast<const HeadMask<MF>::T *>(mask), rows,    \
-                       nact, seed, env->replica_base, draw_index, actions, log_prob, entropy, row_stats, mask_bits)
-#define ONGYM_HEAD_FWD_MODES(DT, MF)                                                                                       \
-    if (mode == ONGYM_HEAD_SAMPLE) ONGYM_HEAD_FWD(DT, ONGYM_HEAD_SAMPLE, MF);                                              \
-    else if (mode == ONGYM_HEAD_ARGMAX) ONGYM_HEAD_FWD(DT, ONGYM_HEAD_ARGMAX, MF);                                         \
-    else ONGYM_HEAD_FWD(DT, ONGYM_HEAD_EVALUATE, MF)
-    if (mask_format == ONGYM_MASK_BYTES) {
-        if (dtype == ONGYM_DTYPE_F32) { ONGYM_HEAD_FWD_MODES(ONGYM_DTYPE_F32, ONGYM_MASK_BYTES); }
-        else { ONGYM_HEAD_FWD_MODES(ONGYM_DTYPE_BF16, ONGYM_MASK_BYTES); }
-    } else {
-        if (dtype == ONGYM_DTYPE_F32) { ONGYM_HEAD_FWD_MODES(ONGYM_DTYPE_F32, ONGYM_MASK_BITS); }
-        else { ONGYM_HEAD_FWD_MODES(ONGYM_DTYPE_BF16, ONGYM_MASK_BITS); }
-    }
-#undef ONGYM_HEAD_FWD_MODES
-#undef ONGYM_HEAD_FWD
+    dispatch<int, ONGYM_MASK_BYTES, ONGYM_MASK_BITS>(mask_format, [&](auto MF) {
+        dispatch<int, ONGYM_DTYPE_F32, ONGYM_DTYPE_BF16>(dtype, [&](auto DT) {
+            dispatch<int, ONGYM_HEAD_SAMPLE, ONGYM_HEAD_ARGMAX, ONGYM_HEAD_EVALUATE>(mode, [&](auto MODE) {
+                hipLaunchKernelGGL((k_head_fwd<DT, MODE, MF>), grid, block, shm, env->stream,
+                                   static_cast<const typename HeadElem<DT>::T *>(logits),
+                                   static_cast<const typename HeadMask<MF>::T *>(mask), rows, nact, seed, env->replica_base,
+                                   draw_index, actions, log_prob, entropy, row_stats, mask_bits);
+            });
+        });
+    });
     HIP_TRY(env, hipGetLastError());
     return ONGYM_OK;
 }
@@ -1418,15 +1357,9 @@ int ongym_gae(ongym_env *env, int32_t steps, const ongym_step_rec *recs, const f
 
 int ongym_policy_actions(ongym_env *env, int32_t policy, int32_t *actions, uint8_t *flags) {
     if (!env || !actions) return env ? fail_arg(env, "null actions") : ONGYM_E_ARG;
-    if (policy < ONGYM_POLICY_FIRST_FIT || policy >= ONGYM_POLICY_COUNT) return fail_arg(env, "unknown policy id");
-    if (policy >= ONGYM_POLICY_LOWEST_SPECTRUM && env->P.k_paths > 8)
-        return fail_arg(env, "this policy supports at most 8 candidate routes", ONGYM_E_LIMIT);
-    if (policy != ONGYM_POLICY_FIRST_FIT && env->P.n_mods_consider < env->P.n_mods)
-        return fail_arg(env, "only the first-fit policy is fused for modulations_to_consider < n_mods", ONGYM_E_LIMIT);
-    if (policy == ONGYM_POLICY_MSCL && (env->P.bit_rate_mode != 0 || env->P.n_bit_rates <= 0))
-        return fail_arg(env, "the MSCL policy sums its capacity loss over the discrete bit rates: bit_rate_mode must be discrete", ONGYM_E_LIMIT);
-    HIP_TRY(env, hipSetDevice(env->cfg.device));
     int rc;
+    if ((rc = check_policy(env, policy))) return rc;
+    HIP_TRY(env, hipSetDevice(env->cfg.device));
     if (env->cfg.io_device) return launch_run(env, kModePolicyOnly, policy, 1, nullptr, actions, flags, nullptr);
     if ((rc = launch_run(env, kModePolicyOnly, policy, 1, nullptr, env->d_act_out, env->d_flag_out, nullptr))) return rc;
     HIP_TRY(env, hipMemcpyAsync(actions, env->d_act_out, (size_t)env->P.batch * 4, hipMemcpyDeviceToHost, env->stream));
@@ -1442,14 +1375,10 @@ static int query(ongym_env *env, int what, int replica, int path, int slot, int 
     if (what == kQPathFree && (slot < 0 || n <= 0 || slot >= env->P.n_slots || n > 1023)) return fail_arg(env, "slot / nslots out of range");
     if (what == kQCandidates && (path <= 0 || path > 1023 || n <= 0 || n > 1023)) return fail_arg(env, "total_slots / nslots out of range");
     HIP_TRY(env, hipSetDevice(env->cfg.device));
-#define ONGYM_LAUNCH_Q(UA, R)                                                                                       \
-    hipLaunchKernelGGL((k_query<UA, R>), dim3(1), dim3(64), env->lds, env->stream, env->d_P, what, replica, path,   \
-                       slot, n, env->d_scratch_i, env->d_scratch_d)
-    if (env->P.uniform_alpha) { if (env->P.rec32) ONGYM_LAUNCH_Q(true, true); else ONGYM_LAUNCH_Q(true, false); }
-    else { if (env->P.rec32) ONGYM_LAUNCH_Q(false, true); else ONGYM_LAUNCH_Q(false, false); }
-#undef ONGYM_LAUNCH_Q
-    HIP_TRY(env, hipGetLastError());
-    return 0;
+    return with_layout(env->P, [&](auto UA, auto R32) {
+        return launch_lds(env, k_query<UA, R32>, dim3(1), env->lds, env->d_P, what, replica, path, slot, n, env->d_scratch_i,
+                          env->d_scratch_d);
+    });
 }
 
 int ongym_query_available(ongym_env *env, int32_t replica, int32_t path_id, int32_t *out) {
@@ -1489,19 +1418,14 @@ int ongym_query_gsnr_many(ongym_env *env, int32_t replica, int32_t count, const 
         return fail_arg(env, "hipMalloc failed", ONGYM_E_HIP);
     }
     hipError_t e = hipMemcpyAsync(d_c, cands, (size_t)count * 3 * sizeof(int32_t), hipMemcpyHostToDevice, env->stream);
-#define ONGYM_LAUNCH_QM(UA, R)                                                                                      \
-    hipLaunchKernelGGL((k_query_gsnr_many<UA, R>), dim3(count), dim3(64), env->lds, env->stream, env->d_P, replica, \
-                       count, d_c, d_o)
-    if (e == hipSuccess) {
-        if (env->P.uniform_alpha) { if (env->P.rec32) ONGYM_LAUNCH_QM(true, true); else ONGYM_LAUNCH_QM(true, false); }
-        else { if (env->P.rec32) ONGYM_LAUNCH_QM(false, true); else ONGYM_LAUNCH_QM(false, false); }
-        e = hipGetLastError();
-    }
-#undef ONGYM_LAUNCH_QM
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_o, (size_t)count * 3 * sizeof(double), hipMemcpyDeviceToHost, env->stream);
+    const int rc = e != hipSuccess ? 0 : with_layout(env->P, [&](auto UA, auto R32) {
+        return launch_lds(env, k_query_gsnr_many<UA, R32>, dim3(count), env->lds, env->d_P, replica, count, d_c, d_o);
+    });
+    if (e == hipSuccess && !rc) e = hipMemcpyAsync(out, d_o, (size_t)count * 3 * sizeof(double), hipMemcpyDeviceToHost, env->stream);
     hipError_t e2 = hipStreamSynchronize(env->stream);
     (void)hipFree(d_c);
     (void)hipFree(d_o);
+    if (rc) return rc;
     if (e != hipSuccess || e2 != hipSuccess) {
         env->err = std::string("ongym_query_gsnr_many: ") + hipGetErrorString(e != hipSuccess ? e : e2);
         return ONGYM_E_HIP;

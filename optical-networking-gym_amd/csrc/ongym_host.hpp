@@ -30,10 +30,10 @@ struct ongym_env {
     bool has_source = false;
     uint64_t replica_base = 0;      // global index of this environment's first replica (ongym_seed_base)
     std::vector<double> cfg_bit_rates;     // host copy of the discrete bit rates
-    bool fast_ok = false;           // the configuration is eligible for k_fast (see fast_eligible)
+    bool fast_ok = false;           // the configuration is eligible for k_fast (decided in build(), ongym_hip.hip)
     bool fast_m64 = false;
     bool fast_wide = true;          // some slot count of the traffic table exceeds 32: the general (`w`) lean kernels run
-    bool fast_lb_ok = false, fast_hsnr_ok = false, fast_lf_ok = false;   // ... and for the lean kernels of the other policies
+    uint32_t lean_policies = 0;     // bit p: policy p's lean unit prepared in build() (its LDS block fits the CU)
     bool trace_used = false;        // a trace the lean kernel cannot replay was installed: its records may not fit the lean codec
     bool trace_fast_ok = false;     // the installed (host) trace only carries bit rates of the configured table
     size_t fast_lds = 0;
@@ -64,11 +64,4 @@ namespace ongym {
 ONGYM_FAST_DECL(0) ONGYM_FAST_DECL(1) ONGYM_FAST_DECL(2) ONGYM_FAST_DECL(10)
 ONGYM_FAST_DECL(0w) ONGYM_FAST_DECL(1w) ONGYM_FAST_DECL(2w) ONGYM_FAST_DECL(10w)
 #undef ONGYM_FAST_DECL
-// fn = fast_prepare / fast_launch / fast_occupancy of policy unit p, narrow or wide build as the environment needs
-#define ONGYM_FAST_CALL(fn, p, env, ...) ((env)->fast_wide ? fn##_p##p##w((env), ##__VA_ARGS__) : fn##_p##p((env), ##__VA_ARGS__))
-// policies with a lean kernel (the ids above)
-inline bool fast_policy_supported(int policy) {
-    return policy == ONGYM_POLICY_FIRST_FIT || policy == ONGYM_POLICY_LOAD_BALANCING || policy == ONGYM_POLICY_HIGHEST_SNR ||
-           policy == ONGYM_POLICY_LOWEST_FRAGMENTATION;
-}
 }

@@ -1454,3 +1454,51 @@ def test_policies_wide_services_41_links_vs_oracle(pid):
         o.seed(77); o.reset(); o.run_policy(0, warm)
         assert_records_equal(got[:, r], o.run_policy(pid, steps), f"policy {pid} replica {r}")
         np.testing.assert_array_equal(env.grid(r), o.grid())
+
+
+@pytest.mark.parametrize("topo,uniform,track", [("nsfnet", True, False), ("nsfnet", True, True), ("nobel-eu", True, False),
+                                                ("nobel-eu", True, True), ("nsfnet", False, False), ("nobel-eu", False, False)],
+                         ids=["ua_r32", "ua_r32_ids", "ua_m64", "ua_m64_ids", "alpha_r32", "alpha_m64"])
+def test_generic_kernels_with_state_above_64k_vs_oracle(topo, uniform, track, monkeypatch):
+    """The generic kernels with a state block above the default 64 KiB LDS limit, which each launch raises for the kernel it
+    runs: the four (uniform attenuation, 32-bit record) layouts of k_run (nsfnet: 22 links, nobel-eu: 41), per-link attenuation,
+    and the id-tracking (DEFRAG) instantiations.  A first-fit warm-up, then policies 0, 1, 2, 3, 10 and 11 in turn on the same
+    replicas (the k_run of every policy class), and GSNR queries (k_query, k_query_gsnr_many): records, grids and GSNR against
+    the oracle."""
+    import copy
+    monkeypatch.setenv("ONGYM_FORCE_GENERIC", "1")
+    tb = golden_tables(topo)
+    if not uniform:
+        tb = copy.deepcopy(tb)
+        tb.link_alpha = tb.link_alpha * np.linspace(0.9, 1.2, tb.n_links)
+    B, warm, steps = 4, 300, 100
+    kw = dict(modulations=jocn_modulations(), num_spectrum_resources=128, capacity=2624 if track else 4864, load=150,
+              bit_rate_selection="discrete", bit_rates=(10, 40, 100, 400), auto_reset=True, episode_length=1000,
+              replica_load=np.linspace(100, 220, B), track_service_ids=track)
+    holder = nat.ConfigHolder(tb, batch=B, **kw)
+    env = BatchedQRMSAEnv(tables=tb, batch_size=B, **kw)
+    occ = env.occupancy()
+    assert not occ["lean_kernel"] and occ["lds_bytes"] > 65536 and occ["blocks_per_cu"] >= 1, occ
+    env.seed(64); env.reset()
+    oracles = []
+    for r in range(B):
+        o = OracleEnv(holder, replica=r)
+        o.seed(64); o.reset()
+        oracles.append(o)
+    policies = (nat.POLICY_FIRST_FIT, nat.POLICY_FIRST_FIT, nat.POLICY_LOAD_BALANCING, nat.POLICY_HIGHEST_SNR,
+                nat.POLICY_LOWEST_SPECTRUM, nat.POLICY_LOWEST_FRAGMENTATION, nat.POLICY_MSCL)
+    for i, pid in enumerate(policies):
+        n = warm if i == 0 else steps
+        got = env.step_policy(n, policy=pid)
+        for r, o in enumerate(oracles):
+            assert_records_equal(got[:, r], o.run_policy(pid, n), f"{topo} policy {pid} (launch {i}) replica {r}")
+            np.testing.assert_array_equal(env.grid(r), o.grid())
+    for r, o in enumerate(oracles):
+        q = env.request(r)
+        p = int(tb.pair_paths[q["source"], q["destination"], 0])
+        starts = o.candidates(o.available(p), 4)
+        assert starts
+        cands = [(p, s0, 4) for s0 in starts[:3]]
+        want = np.array([o.gn(*c) for c in cands])
+        np.testing.assert_allclose(env.gsnr_many(r, cands), want, rtol=GSNR_RTOL)
+        np.testing.assert_allclose(env.gsnr(r, *cands[-1]), want[-1], rtol=GSNR_RTOL)
