@@ -867,10 +867,16 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                 }
             };
             // pass 2: 1/GSNR of ONE candidate (start `first`, width nn) with lanes over the interferers.  Every lane finishes the
-            // evaluation for ITS (bit rate, format) entry of the per-lane tables l_*; lane q is the one that counts.  Returns
-            // the decision of qot_ok; ev_acc (and ev_ase / ev_nli when records are written) hold lane q's values when it passes.
-            auto eval_one = [&](int first, int nn, int q, const PathRec &pr, double l_a, double l_b, double l_d, double l_nlic,
-                                double l_lo, double l_hi) -> int {
+            // evaluation for ITS (bit rate, format) entry of the per-lane tables l_*; lane q is the one the walk is at.
+            // The sum depends on the centre 2 first + nn alone, and first fit's start on nn alone: every format of width nn that
+            // the walk would visit next (`rest`: the feasible formats below q's, as bits of the modulation index) would be
+            // evaluated at the same start with the same sum, and its lane already holds its own exact decision.  So the formats
+            // of width nn that follow q in the walk, up to the first feasible format of another width (FIRST_FIT and
+            // LOAD_BALANCING; `rest` = 0 decides lane q alone), are decided here too, in walk order, and counted as the serial
+            // walk counts them: one evaluation each, up to the one that passes.  Returns the lane of the format that passes, or
+            // -1 (`rest` then loses the formats decided); ev_acc (and ev_ase / ev_nli when records are written) hold its values.
+            auto eval_one = [&](int first, int nn, int q, uint32_t &rest, const PathRec &pr, double l_a, double l_b, double l_d,
+                                double l_nlic, double l_lo, double l_hi) -> int {
                 const uint32_t c2 = (uint32_t)(2 * first + nn);
                 double part = 0.0;
                 {
@@ -886,38 +892,47 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
     #pragma unroll              // (a group without interferers has zero weights and zero table values: no select needed)
                     for (int e = 0; e < ENT; e++) part = fma(t[e].x, e_w1[e], fma(-t[e].y, e_pw2[e], part));
                 }
-                lane_terms += e_terms;
+                int x_terms = 0;        // interferer-link terms beyond the register cache
                 for (int base = kWave * ENT; base < L; base += kWave) {       // interferers beyond the register cache
                     const int j = base + lane;
                     if (j < L) {
                         uint32_t c2k, key4;
                         double w1, pw2;
-                        lane_terms += intf_of(list[j], pr.mask_lo, pr.mask_hi, c2k, key4, w1, pw2);
+                        x_terms += intf_of(list[j], pr.mask_lo, pr.mask_hi, c2k, key4, w1, pw2);
                         const uint32_t adi = __builtin_amdgcn_sad_u16(c2k, c2, 0);
                         const TabPair t = load_pair(tab, key4 | (adi << 4));
                         part += t.x * w1 - t.y * pw2;
                     }
                 }
-                d_evals++;
                 const double tot = wave_sum_eval(part);
                 const double g_nli = fma(l_nlic, tot, l_d);
                 const double g_ase = fma(l_b, (double)first, l_a);                  // envs/qrmsa.pyx:901-905, see lane_fac
                 const double acc = g_ase + g_nli;
-                int ok;
-                {
-                    const uint64_t yes = __ballot(acc <= l_lo), no = __ballot(acc >= l_hi);
-                    if ((yes >> q) & 1ull) ok = 1;
-                    else if ((no >> q) & 1ull) ok = 0;
-                    else {      // inside the 1e-9 band: the reference's own dB-domain expression (see qot_ok)
-                        const uint64_t db = __ballot(10.0 * log10(1.0 / acc) >= P.mod_thr[lane & 7] + *KC(&ge->margin));
-                        ok = (int)((db >> q) & 1ull);
+                int ln = q, walked = 1;
+                const uint64_t yes = __ballot(acc <= l_lo);
+                if (!((yes >> q) & 1ull)) {
+                    uint64_t grp = 1ull << q;
+                    if (rest) {     // the walk's next formats of width nn, up to the first of another width
+                        const uint32_t same = (uint32_t)(__ballot(w_n == nn) >> (8 * cur_bi)) & rest, other = rest & ~same;
+                        const uint32_t g = other ? same & (~0u << (32 - __builtin_clz(other))) : same;
+                        grp |= (uint64_t)g << (8 * cur_bi);
                     }
+                    // inside the 1e-9 band: the reference's own dB-domain expression (see qot_ok)
+                    const uint64_t band = grp & ~(yes | __ballot(acc >= l_hi));
+                    uint64_t pass = grp & yes;
+                    if (band) pass |= band & __ballot(10.0 * log10(1.0 / acc) >= P.mod_thr[lane & 7] + *KC(&ge->margin));
+                    ln = pass ? 63 - __builtin_clzll(pass) : -1;                  // the highest format first
+                    walked = __popcll(pass ? grp >> ln : grp);
+                    if (!pass) rest &= ~(uint32_t)(grp >> (8 * cur_bi));
                 }
-                if (ok) {
-                    ev_acc = readlane_f64(acc, q);
-                    if (REC) { ev_ase = readlane_f64(g_ase, q); ev_nli = readlane_f64(g_nli, q); }
+                d_evals += walked;
+                lane_terms += e_terms + x_terms;
+                if (walked > 1) lane_terms += (walked - 1) * (e_terms + x_terms);
+                if (ln >= 0) {
+                    ev_acc = readlane_f64(acc, ln);
+                    if (REC) { ev_ase = readlane_f64(g_ase, ln); ev_nli = readlane_f64(g_nli, ln); }
                 }
-                return ok;
+                return ln;
             };
             // HIGHEST_SNR / LOWEST_FRAGMENTATION: the set bits of `v` (run-AND words, lane w = word w) as ascending slot indices in
             // dense lanes (xlist); returns their number
@@ -1081,10 +1096,12 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                     FSTAMP(15);
                     continue;
                 }
-                const int ok = eval_one(first, nn, q, pr, r_a, r_b, r_d, w_nlic, w_lim_lo, w_lim_hi);
+                uint32_t none = 0;
+                const int ln = eval_one(first, nn, q, POL == ONGYM_POLICY_LOWEST_FRAGMENTATION ? none : feas, pr, r_a, r_b, r_d, w_nlic,
+                                        w_lim_lo, w_lim_hi);
                 FSTAMP(5);
-                if (ok) {
-                    ch_k = k; ch_m = m; ch_slot = first; ch_n = n; ch_path = path;
+                if (ln >= 0) {          // all formats of the group have n slots
+                    ch_k = k; ch_m = ln & 7; ch_slot = first; ch_n = n; ch_path = path;
                     ch_mask = pmask;
                     ch_acc = ev_acc; ch_ase = ev_ase; ch_nli = ev_nli;
                     break;
@@ -1104,7 +1121,9 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                 // more): the reference raises ValueError if that fails (envs/qrmsa.pyx:925-929) — a fused episode rejects the
                 // request and flags it (as k_run does).  Same route: the interferer cache is the one just used.
                 const LaneFac sf = lane_fac(t_n, t_nlic, t_selfa);
-                if (eval_one(ch_slot, ch_n, 8 * cur_bi + ch_m, pr, sf.c1 * pr.ase, sf.cb * pr.ase, sf.c2 * pr.w1, t_nlic, t_lim_lo, t_lim_hi)) {
+                uint32_t none = 0;
+                if (eval_one(ch_slot, ch_n, 8 * cur_bi + ch_m, none, pr, sf.c1 * pr.ase, sf.cb * pr.ase, sf.c2 * pr.w1, t_nlic, t_lim_lo,
+                             t_lim_hi) >= 0) {
                     ch_acc = ev_acc; ch_ase = ev_ase; ch_nli = ev_nli;
                 } else { ch_k = -1; lf_qot = true; }
                 break;
