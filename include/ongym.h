@@ -386,6 +386,48 @@ int ongym_query_request(ongym_env *env, int32_t replica, ongym_request *out);
 /* per-replica counters: out[batch] (host buffer) */
 int ongym_stats_get(ongym_env *env, ongym_stats *out);
 
+/* Save, restore and fork replica states.  A replica's state is everything that decides its future:
+ *   its slot bitmap; its service records (with ids, OSNR and the last step's move log where cfg.defragmentation or
+ *   cfg.track_service_ids keeps them); the clock and the pending request (cur_*, have_request); the request counter and the
+ *   stream key; the per-replica parameters (launch power, margin, mean inter-arrival time); the running-OSNR accumulators;
+ *   and every ongym_stats field (max_modulation_idx, which the action codec is relative to, and the terminal-step snapshot
+ *   included) EXCEPT the work counters total_steps .. total_active_sum: they count work done in THIS environment, so they
+ *   stay with the destination replica and keep counting.
+ * Flags of a load or fork:
+ *   ONGYM_STATE_KEEP_STREAM  the destination keeps its own stream key.  The pending request, the clock and the request counter
+ *                            still come from the source (release times are absolute), so the requests after the pending one
+ *                            are drawn from the destination's stream at the source's counter: independent futures of one state.
+ *   ONGYM_STATE_KEEP_PARAMS  the destination keeps its launch power, margin and load (mean inter-arrival time): one loaded
+ *                            network forked into a power or load sweep.
+ * Trace sources (ongym_set_requests): the cursor travels, the rows do not; each replica goes on reading its own row.
+ * Request source of the destination: ongym_seed and ongym_set_requests rewind every replica's counter, so they come BEFORE a
+ * load.  A destination without a source takes the device generator when the load covers all its replicas and the blob comes
+ * from a device-generator environment (the keys and counters travel); any other load into it fails with ONGYM_E_STATE.
+ * A blob saved by an environment that replayed a trace the lean kernels cannot run (bit rates outside the configured table,
+ * or a device trace) carries that fact: the destination then runs the generic kernels from the load on, as the source did.
+ * Python-side counters (such as the draw counter of the action head's helper) are not device state.
+ *
+ * The blob (out / in): a device pointer when cfg.io_device = 1 (16-byte aligned, e.g. a torch uint8 tensor), a host pointer
+ * otherwise; ongym_state_size bytes: a 256-byte header (magic, format version, configuration fingerprint, layout facts: record
+ * codec, id tracking, row words, links, capacity, sizeof of the per-replica block, section sizes and offsets, count), then
+ * `count` replica blocks, each section 16-byte aligned.  A blob loads into any environment whose ongym_config agrees on every
+ * field but batch, device, io_device, launch_power_w, margin, load and the replica_* arrays (the tables are compared by
+ * content); anything else is refused with ONGYM_E_ARG and an ongym_last_error text.
+ * replicas: host int32 [count] (NULL = all `batch` replicas in order, count must then equal batch), entries in [0, batch); a
+ * load list must not repeat an entry.  count lies in [1, batch].  Everything is checked before any launch.
+ * Streams: save and load run on the env's stream.  Load reads the header on the host first: for a device blob that is one
+ * small device-to-host copy, which waits for the stream.  Calls with host blobs synchronise. */
+enum { ONGYM_STATE_KEEP_STREAM = 1, ONGYM_STATE_KEEP_PARAMS = 2 };
+int ongym_state_size(ongym_env *env, int32_t count, int64_t *bytes);      /* header + count replica blocks */
+int ongym_state_save(ongym_env *env, int32_t count, const int32_t *replicas, void *out);
+int ongym_state_load(ongym_env *env, int32_t count, const int32_t *replicas, const void *in, int32_t flags);
+/* The in-loop gather: replica j takes the PRE-fork state of replica src[j], whatever the overlap (permutations, cycles,
+ * one replica into all).  src[j] < 0, src[j] == j or src[j] >= batch leaves replica j unchanged.  src int32 [batch] follows
+ * cfg.io_device: a device list is read on the env's stream and nothing synchronises (its entries cannot be checked); a host
+ * list with an entry >= batch is refused with ONGYM_E_ARG before any launch.  Runs in one pass into a second set of state
+ * arrays (allocated on the first fork: twice the state memory from then on), which then becomes the environment's. */
+int ongym_fork(ongym_env *env, const int32_t *src, int32_t flags);
+
 /* Diagnostic: resident workgroups (one wavefront = one replica each) per compute unit of the kernel that
  * ongym_step_policy(ONGYM_POLICY_FIRST_FIT) launches on this environment, its dynamic LDS bytes per replica, and whether it
  * is the lean kernel (1) or the generic one (0). */

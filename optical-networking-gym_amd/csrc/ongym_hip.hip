@@ -21,6 +21,7 @@
 #include "ongym_scored.hpp"
 #include "ongym_policy_head.hpp"   // masked categorical action head (ongym_masked_categorical)
 #include "ongym_gae.hpp"           // GAE over a rollout (ongym_gae)
+#include "ongym_state.hpp"         // save / restore / fork of replica states (ongym_state_*, ongym_fork)
 
 using namespace ongym;
 
@@ -841,6 +842,171 @@ static int build(ongym_env *env, const ongym_config *c) {
     return push_params(env);
 }
 
+// ---- save / restore / fork of replica states (kernels: ongym_state.hpp) ----
+// 64-bit FNV-1a over every ongym_config field a saved state depends on, with the tables' contents (not their addresses).
+// Left out: batch, device, io_device, launch_power_w, margin, load and the replica_* arrays (they travel in the state or stay).
+struct Fnv64 {
+    uint64_t h = 1469598103934665603ull;
+    void bytes(const void *p, size_t n) {
+        const unsigned char *c = static_cast<const unsigned char *>(p);
+        for (size_t i = 0; i < n; i++) { h ^= c[i]; h *= 1099511628211ull; }
+    }
+    template <class T> void val(T v) { bytes(&v, sizeof v); }
+    template <class T> void tab(const T *p, size_t n) {
+        val<uint64_t>(p ? (uint64_t)n : ~0ull);
+        if (p && n) bytes(p, n * sizeof(T));
+    }
+};
+
+static uint64_t state_fingerprint(const ongym_config *c) {
+    Fnv64 f;
+    const size_t N = (size_t)c->n_nodes, E = (size_t)c->n_links, NP = (size_t)c->n_paths, M = (size_t)c->n_mods;
+    const int32_t ints[] = {c->struct_size, c->abi_version, c->n_nodes, c->n_links, c->n_paths, c->k_paths, c->max_hops,
+                            c->n_mods, c->n_slots, c->capacity, c->episode_length, c->auto_reset, c->bit_rate_mode,
+                            c->n_bit_rates, c->bit_rate_lo, c->bit_rate_hi, c->measure_disruptions, c->defragmentation,
+                            c->n_defrag_services, c->track_service_ids, c->n_mods_consider};
+    for (int32_t v : ints) f.val(v);
+    const double dbls[] = {c->frequency_start, c->slot_bandwidth, c->channel_width, c->mean_holding_time, c->max_bit_rate,
+                           c->nslots_channel_width};
+    for (double v : dbls) f.val(v);
+    f.tab(c->pair_paths, N * N * (size_t)c->k_paths);
+    f.tab(c->path_hops, NP);
+    f.tab(c->path_links, NP * (size_t)c->max_hops);
+    f.tab(c->link_nspans, E); f.tab(c->link_span_km, E); f.tab(c->link_alpha, E); f.tab(c->link_nf, E);
+    f.tab(c->mod_se, M); f.tab(c->mod_min_osnr, M);
+    const bool discrete = c->bit_rate_mode == 0;
+    f.tab(discrete ? c->bit_rates : nullptr, (size_t)c->n_bit_rates);
+    f.tab(discrete ? c->bit_rate_cum : nullptr, (size_t)c->n_bit_rates);
+    f.tab(c->node_cum, N);
+    f.tab(c->path_len_norm, NP);
+    return f.h;
+}
+
+static StateArrays state_arrays(const Params &P) {
+    StateArrays a{};
+    a.base[kSecOcc] = reinterpret_cast<unsigned char *>(P.occ);
+    a.base[kSecSvcA] = reinterpret_cast<unsigned char *>(P.svc_a);
+    a.base[kSecSvcB] = reinterpret_cast<unsigned char *>(P.svc_b);
+    a.base[kSecSvcR] = reinterpret_cast<unsigned char *>(P.svc_r);
+    a.base[kSecSvcQ] = reinterpret_cast<unsigned char *>(P.svc_q);
+    a.base[kSecSvcO] = reinterpret_cast<unsigned char *>(P.svc_o);
+    a.base[kSecMoveLog] = reinterpret_cast<unsigned char *>(P.move_log);
+    a.base[kSecMoveN] = reinterpret_cast<unsigned char *>(P.move_n);
+    a.base[kSecEnv] = reinterpret_cast<unsigned char *>(P.env);
+    return a;
+}
+
+static void set_state_arrays(Params &P, void *const base[kStateSections]) {
+    P.occ = static_cast<uint64_t *>(base[kSecOcc]);
+    P.svc_a = static_cast<uint32_t *>(base[kSecSvcA]);
+    P.svc_b = static_cast<uint32_t *>(base[kSecSvcB]);
+    P.svc_r = static_cast<float *>(base[kSecSvcR]);
+    P.svc_q = static_cast<uint32_t *>(base[kSecSvcQ]);
+    P.svc_o = static_cast<double *>(base[kSecSvcO]);
+    P.move_log = static_cast<ongym_move *>(base[kSecMoveLog]);
+    P.move_n = static_cast<int32_t *>(base[kSecMoveN]);
+    P.env = static_cast<DevEnv *>(base[kSecEnv]);
+}
+
+static StateLayout state_layout(const Params &P) {
+    StateLayout L{};
+    const int64_t C = P.capacity, ids = P.track_ids ? 1 : 0;
+    const int64_t bytes[kStateSections] = {(int64_t)P.n_links * P.row_words * 8, C * 4, C * 4, C * 4, ids * C * 4, ids * C * 8,
+                                           ids * ONGYM_MOVE_LOG * (int64_t)sizeof(ongym_move), ids * 4, (int64_t)sizeof(DevEnv)};
+    int64_t off = 0;
+    int32_t items = 0;
+    for (int s = 0; s < kStateSections; s++) {
+        L.bytes[s] = bytes[s];
+        L.off[s] = off;
+        off += (bytes[s] + 15) & ~(int64_t)15;
+        L.shift[s] = s == kSecEnv ? 3 : bytes[s] % 16 == 0 ? 4 : bytes[s] % 8 == 0 ? 3 : 2;   // DevEnv: 8-byte words (kept words)
+        L.prefix[s] = items;
+        items += (int32_t)(bytes[s] >> L.shift[s]);
+    }
+    L.prefix[kStateSections] = items;
+    L.block_bytes = off;
+    return L;
+}
+
+static StateHeader state_header(const ongym_env *env, const StateLayout &L, int32_t count) {
+    StateHeader h;
+    memset(&h, 0, sizeof h);
+    memcpy(h.magic, "ONGYMST", 8);
+    h.format = kStateFormat;
+    h.header_bytes = (uint32_t)sizeof(StateHeader);
+    h.fingerprint = env->state_fp;
+    h.count = count;
+    h.block_bytes = L.block_bytes;
+    h.rec32 = env->P.rec32; h.track_ids = env->P.track_ids; h.row_words = env->P.row_words; h.n_links = env->P.n_links;
+    h.capacity = env->P.capacity; h.devenv_bytes = (int32_t)sizeof(DevEnv); h.n_sections = kStateSections;
+    h.trace_used = env->trace_used ? 1 : 0;
+    h.req_mode = env->P.req_mode;
+    for (int s = 0; s < kStateSections; s++) { h.sec_bytes[s] = L.bytes[s]; h.sec_off[s] = L.off[s]; }
+    return h;
+}
+
+// DevEnv words (bit w = word w) the destination of a load or fork keeps: always the work counters total_*, plus the stream key
+// (ONGYM_STATE_KEEP_STREAM) or the per-replica parameters (ONGYM_STATE_KEEP_PARAMS)
+static void state_keep_mask(int32_t flags, uint64_t &lo, uint64_t &hi) {
+    static_assert(offsetof(ongym_stats, total_active_sum) == offsetof(ongym_stats, total_steps) + 7 * 8, "total_* are 8 int64");
+    static_assert(offsetof(DevEnv, margin) == 8 && offsetof(DevEnv, mean_iat) == 16 && offsetof(DevEnv, mean_iat_f) == 24,
+                  "the parameters are the first four words of DevEnv");
+    lo = hi = 0;
+    auto set = [&](size_t off, size_t n) {
+        for (size_t w = off / 8; w < (off + n + 7) / 8; w++) (w < 64 ? lo : hi) |= 1ull << (w & 63);
+    };
+    set(offsetof(DevEnv, st) + offsetof(ongym_stats, total_steps), 8 * 8);
+    if (flags & ONGYM_STATE_KEEP_STREAM) set(offsetof(DevEnv, rng_key), 8);
+    if (flags & ONGYM_STATE_KEEP_PARAMS) set(offsetof(DevEnv, launch_power), 28);
+}
+
+// count in [1, batch]; a NULL list means all replicas (count == batch); entries in [0, batch), distinct when `distinct`
+static int check_state_list(ongym_env *env, int32_t count, const int32_t *replicas, bool distinct) {
+    const int B = env->P.batch;
+    if (count < 1 || count > B) return fail_arg(env, "state count must lie in [1, batch]");
+    if (!replicas) return count == B ? 0 : fail_arg(env, "a NULL replica list means all replicas: count must equal batch");
+    std::vector<char> seen(distinct ? (size_t)B : 0, 0);
+    for (int32_t k = 0; k < count; k++) {
+        const int32_t r = replicas[k];
+        if (r < 0 || r >= B) return fail_arg(env, "replica list entry outside [0, batch)");
+        if (distinct) {
+            if (seen[(size_t)r]) return fail_arg(env, "a load list must not repeat a replica");
+            seen[(size_t)r] = 1;
+        }
+    }
+    return 0;
+}
+
+// the host list -> d_state_idx (stream-ordered: a launch of an earlier call that reads it has been issued before)
+static int upload_state_list(ongym_env *env, int32_t count, const int32_t *list) {
+    if (!env->d_state_idx) {
+        int rc = dev_alloc(env, (size_t)env->P.batch, &env->d_state_idx, false);
+        if (rc) return rc;
+    }
+    HIP_TRY(env, hipMemcpyAsync(env->d_state_idx, list, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, env->stream));
+    return 0;
+}
+
+static int ensure_state_stage(ongym_env *env, size_t bytes) {
+    if (env->state_stage_bytes >= bytes) return 0;
+    if (env->d_state_stage) {
+        HIP_TRY(env, hipStreamSynchronize(env->stream));
+        (void)hipFree(env->d_state_stage);
+        env->d_state_stage = nullptr;
+        env->state_stage_bytes = 0;
+    }
+    HIP_TRY(env, hipMalloc(&env->d_state_stage, bytes));
+    env->state_stage_bytes = bytes;
+    return 0;
+}
+
+template <int MODE>
+static int launch_state_copy(ongym_env *env, int blocks, const StateCopyArgs &a) {
+    hipLaunchKernelGGL(k_state_copy<MODE>, dim3(blocks), dim3(kStateThreads), 0, env->stream, a);
+    HIP_TRY(env, hipGetLastError());
+    return 0;
+}
+
 extern "C" {
 
 int32_t ongym_abi_version(void) { return ONGYM_ABI_VERSION; }
@@ -889,6 +1055,7 @@ int ongym_create(const ongym_config *cfg, ongym_env **out) {
         ongym_destroy(env);
         return rc;
     }
+    env->state_fp = state_fingerprint(cfg);
     *out = env;
     return ONGYM_OK;
 }
@@ -901,6 +1068,7 @@ void ongym_destroy(ongym_env *env) {
     if (env->d_trace) (void)hipFree(env->d_trace);
     if (env->d_out) (void)hipFree(env->d_out);
     if (env->h_pinned) (void)hipHostFree(env->h_pinned);
+    if (env->d_state_stage) (void)hipFree(env->d_state_stage);
     if (env->ev0) (void)hipEventDestroy(env->ev0);
     if (env->ev1) (void)hipEventDestroy(env->ev1);
     if (env->own_stream) (void)hipStreamDestroy(env->own_stream);      // a caller's stream (ongym_set_stream) is the caller's
@@ -1516,6 +1684,148 @@ int ongym_stats_get(ongym_env *env, ongym_stats *out) {
     for (size_t r = 0; r < host.size(); r++) { out[r] = host[r].st; flags |= host[r].st.flags; }
     if (flags & ONGYM_F_OVERFLOW) { env->err = "a replica overflowed its service table (raise capacity)"; return ONGYM_E_CAPACITY; }
     return ONGYM_OK;
+}
+
+// ---- save / restore / fork of replica states ----
+int ongym_state_size(ongym_env *env, int32_t count, int64_t *bytes) {
+    if (!env || !bytes) return env ? fail_arg(env, "null bytes") : ONGYM_E_ARG;
+    if (count < 1 || count > env->P.batch) return fail_arg(env, "state count must lie in [1, batch]");
+    *bytes = (int64_t)sizeof(StateHeader) + (int64_t)count * state_layout(env->P).block_bytes;
+    return ONGYM_OK;
+}
+
+int ongym_state_save(ongym_env *env, int32_t count, const int32_t *replicas, void *out) {
+    if (!env || !out) return env ? fail_arg(env, "null state buffer") : ONGYM_E_ARG;
+    if (int rc = check_state_list(env, count, replicas, false)) return rc;
+    if (env->cfg.io_device && (uintptr_t)out % 16) return fail_arg(env, "a device state buffer must be 16-byte aligned");
+    HIP_TRY(env, hipSetDevice(env->cfg.device));
+    const StateLayout L = state_layout(env->P);
+    const size_t total = sizeof(StateHeader) + (size_t)count * (size_t)L.block_bytes;
+    unsigned char *blob = static_cast<unsigned char *>(out);
+    if (!env->cfg.io_device) {
+        if (int rc = ensure_state_stage(env, total)) return rc;
+        blob = static_cast<unsigned char *>(env->d_state_stage);
+    }
+    if (replicas)
+        if (int rc = upload_state_list(env, count, replicas)) return rc;
+    StateCopyArgs a{};
+    a.L = L;
+    a.cur = state_arrays(env->P);
+    a.blob = blob + sizeof(StateHeader);
+    a.hdr_out = blob;
+    a.list = replicas ? env->d_state_idx : nullptr;
+    a.batch = env->P.batch;
+    a.hdr = state_header(env, L, count);
+    if (int rc = launch_state_copy<kCopyPack>(env, count, a)) return rc;
+    if (!env->cfg.io_device) {
+        HIP_TRY(env, hipMemcpyAsync(out, blob, total, hipMemcpyDeviceToHost, env->stream));
+        HIP_TRY(env, hipStreamSynchronize(env->stream));
+    }
+    return ONGYM_OK;
+}
+
+int ongym_state_load(ongym_env *env, int32_t count, const int32_t *replicas, const void *in, int32_t flags) {
+    if (!env || !in) return env ? fail_arg(env, "null state buffer") : ONGYM_E_ARG;
+    if (flags & ~(ONGYM_STATE_KEEP_STREAM | ONGYM_STATE_KEEP_PARAMS)) return fail_arg(env, "unknown ONGYM_STATE_* flag");
+    if (int rc = check_state_list(env, count, replicas, true)) return rc;
+    if (env->cfg.io_device && (uintptr_t)in % 16) return fail_arg(env, "a device state buffer must be 16-byte aligned");
+    HIP_TRY(env, hipSetDevice(env->cfg.device));
+    StateHeader h;
+    if (env->cfg.io_device) {   // one small device-to-host copy: waits for the stream
+        HIP_TRY(env, hipMemcpyAsync(&h, in, sizeof h, hipMemcpyDeviceToHost, env->stream));
+        HIP_TRY(env, hipStreamSynchronize(env->stream));
+    } else {
+        memcpy(&h, in, sizeof h);
+    }
+    const StateLayout L = state_layout(env->P);
+    const StateHeader want = state_header(env, L, count);
+    if (memcmp(h.magic, want.magic, sizeof h.magic) || h.format != want.format || h.header_bytes != want.header_bytes)
+        return fail_arg(env, "not a state blob of this library (bad magic, format or header size)");
+    if (h.fingerprint != want.fingerprint)
+        return fail_arg(env, "state blob was saved by an environment with another configuration (fingerprint mismatch: "
+                             "topology, tables, slots, capacity or traffic differ)");
+    if (h.rec32 != want.rec32 || h.track_ids != want.track_ids || h.row_words != want.row_words || h.n_links != want.n_links ||
+        h.capacity != want.capacity || h.devenv_bytes != want.devenv_bytes || h.n_sections != want.n_sections ||
+        h.block_bytes != want.block_bytes || memcmp(h.sec_bytes, want.sec_bytes, sizeof h.sec_bytes) ||
+        memcmp(h.sec_off, want.sec_off, sizeof h.sec_off))
+        return fail_arg(env, "state blob layout differs from this build's (record codec, id tracking, row words, capacity or "
+                             "sizeof(DevEnv))");
+    if (h.count != count) return fail_arg(env, "state blob holds another number of replicas than count");
+    // a destination without a request source adopts the device generator when every replica comes from one (the blob carries
+    // the stream keys and counters); anything else needs ongym_seed / ongym_set_requests BEFORE the load (both rewind counters)
+    const bool adopt_rng = !env->has_source && h.req_mode == kReqRng && count == env->P.batch;
+    if (!env->has_source && !adopt_rng)
+        return fail_arg(env, "no request source: call ongym_seed or ongym_set_requests before ongym_state_load (a load of all "
+                             "replicas from a device-generator environment sets it)", ONGYM_E_STATE);
+    if (adopt_rng && (flags & ONGYM_STATE_KEEP_STREAM))
+        return fail_arg(env, "ONGYM_STATE_KEEP_STREAM needs a request source on the destination", ONGYM_E_STATE);
+    const unsigned char *blob = static_cast<const unsigned char *>(in);
+    if (!env->cfg.io_device) {
+        const size_t total = sizeof(StateHeader) + (size_t)count * (size_t)L.block_bytes;
+        if (int rc = ensure_state_stage(env, total)) return rc;
+        HIP_TRY(env, hipMemcpyAsync(env->d_state_stage, in, total, hipMemcpyHostToDevice, env->stream));
+        HIP_TRY(env, hipStreamSynchronize(env->stream));
+        blob = static_cast<const unsigned char *>(env->d_state_stage);
+    }
+    if (replicas)
+        if (int rc = upload_state_list(env, count, replicas)) return rc;
+    StateCopyArgs a{};
+    a.L = L;
+    a.cur = state_arrays(env->P);
+    a.blob = const_cast<unsigned char *>(blob) + sizeof(StateHeader);
+    a.list = replicas ? env->d_state_idx : nullptr;
+    a.batch = env->P.batch;
+    state_keep_mask(flags, a.keep_lo, a.keep_hi);
+    // records of a trace the lean kernels cannot replay may exceed the lean codec (slot counts past its tables, bit rates
+    // outside the configured table): the destination keeps the generic kernels from now on, as ongym_set_requests does
+    if (h.trace_used) env->trace_used = true;
+    if (adopt_rng) {
+        env->P.req_mode = kReqRng;
+        env->has_source = true;
+        if (int rc = push_params(env)) return rc;
+    }
+    return launch_state_copy<kCopyUnpack>(env, count, a);
+}
+
+int ongym_fork(ongym_env *env, const int32_t *src, int32_t flags) {
+    if (!env || !src) return env ? fail_arg(env, "null src") : ONGYM_E_ARG;
+    if (flags & ~(ONGYM_STATE_KEEP_STREAM | ONGYM_STATE_KEEP_PARAMS)) return fail_arg(env, "unknown ONGYM_STATE_* flag");
+    const int B = env->P.batch;
+    if (!env->cfg.io_device)
+        for (int j = 0; j < B; j++)
+            if (src[j] >= B) return fail_arg(env, "fork source entry >= batch");
+    HIP_TRY(env, hipSetDevice(env->cfg.device));
+    const StateLayout L = state_layout(env->P);
+    if (!env->state_alt[kSecEnv]) {   // the second set of state arrays, once: all sections or none
+        void *p[kStateSections] = {};
+        for (int s = 0; s < kStateSections; s++) {
+            if (!L.bytes[s]) continue;
+            const hipError_t e = hipMalloc(&p[s], (size_t)B * (size_t)L.bytes[s]);
+            if (e != hipSuccess) {
+                for (int q = 0; q < s; q++) if (p[q]) (void)hipFree(p[q]);
+                env->err = std::string("hipMalloc of the fork's state arrays: ") + hipGetErrorString(e);
+                return ONGYM_E_HIP;
+            }
+        }
+        for (int s = 0; s < kStateSections; s++)
+            if (p[s]) { env->allocs.push_back(p[s]); env->state_alt[s] = p[s]; }
+    }
+    if (!env->cfg.io_device)
+        if (int rc = upload_state_list(env, B, src)) return rc;
+    StateCopyArgs a{};
+    a.L = L;
+    a.cur = state_arrays(env->P);
+    for (int s = 0; s < kStateSections; s++) a.alt.base[s] = static_cast<unsigned char *>(env->state_alt[s]);
+    a.list = env->cfg.io_device ? src : env->d_state_idx;
+    a.batch = B;
+    state_keep_mask(flags, a.keep_lo, a.keep_hi);
+    if (int rc = launch_state_copy<kCopyGather>(env, B, a)) return rc;
+    // every replica now lives in the other set: swap the sets (the kernels and queries read the arrays through Params)
+    void *old[kStateSections];
+    for (int s = 0; s < kStateSections; s++) old[s] = a.cur.base[s];
+    set_state_arrays(env->P, env->state_alt);
+    for (int s = 0; s < kStateSections; s++) env->state_alt[s] = old[s];
+    return push_params(env);
 }
 
 #ifdef ONGYM_STAMPS

@@ -37,6 +37,11 @@ struct ongym_env {
     bool trace_used = false;        // a trace the lean kernel cannot replay was installed: its records may not fit the lean codec
     bool trace_fast_ok = false;     // the installed (host) trace only carries bit rates of the configured table
     size_t fast_lds = 0;
+    // save / restore / fork of replica states (ongym_state.hpp)
+    uint64_t state_fp = 0;          // fingerprint of the configuration (computed at create from the tables' contents)
+    void *state_alt[9] = {};        // ongym_fork: the second set of state arrays (lazily allocated; swapped with Params' set)
+    int32_t *d_state_idx = nullptr; // [batch] replica list of a save / load, or a host fork list
+    void *d_state_stage = nullptr; size_t state_stage_bytes = 0;   // device copy of a host blob
 };
 
 #define HIP_TRY(env, expr)                                                                               \

@@ -27,6 +27,7 @@ F_BLOCKED_RESOURCES, F_BLOCKED_OSNR, F_QOT_ERROR, F_OVERFLOW, F_NO_REQUEST = 1, 
 DTYPE_F32, DTYPE_BF16 = 0, 1                                # ongym_masked_categorical logits dtypes
 HEAD_SAMPLE, HEAD_ARGMAX, HEAD_EVALUATE = 0, 1, 2           # ... and modes
 MASK_BYTES, MASK_BITS = 0, 1                                # ongym_masked_categorical_rows mask formats
+STATE_KEEP_STREAM, STATE_KEEP_PARAMS = 1, 2                # ongym_state_load / ongym_fork flags
 
 _i32p, _f64p = C.POINTER(C.c_int32), C.POINTER(C.c_double)
 
@@ -223,6 +224,14 @@ def _declare(lib):
     lib.ongym_masked_categorical_backward_rows.restype = C.c_int32
     lib.ongym_gae.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_float, C.c_float, vp, vp]
     lib.ongym_gae.restype = C.c_int32
+    lib.ongym_state_size.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64)]
+    lib.ongym_state_size.restype = C.c_int32
+    lib.ongym_state_save.argtypes = [vp, C.c_int32, vp, vp]
+    lib.ongym_state_save.restype = C.c_int32
+    lib.ongym_state_load.argtypes = [vp, C.c_int32, vp, vp, C.c_int32]
+    lib.ongym_state_load.restype = C.c_int32
+    lib.ongym_fork.argtypes = [vp, vp, C.c_int32]
+    lib.ongym_fork.restype = C.c_int32
     lib.ongym_query_available.argtypes = [vp, C.c_int32, C.c_int32, vp]
     lib.ongym_query_gsnr.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]
     lib.ongym_query_gsnr_many.argtypes = [vp, C.c_int32, C.c_int32, vp, vp]
@@ -264,7 +273,7 @@ def _declare_tail(lib, vp, skip=()):
 EXPORTED_SYMBOLS = (
     "ongym_create", "ongym_destroy", "ongym_seed", "ongym_seed_base", "ongym_set_requests", "ongym_reset", "ongym_reset_episode_counters", "ongym_step_policy",
     "ongym_step_actions", "ongym_step_actions_bundle", "ongym_policy_actions", "ongym_observe", "ongym_sample_actions", "ongym_masked_categorical", "ongym_masked_categorical_backward",
-    "ongym_masked_categorical_rows", "ongym_masked_categorical_backward_rows", "ongym_gae", "ongym_query_available", "ongym_query_gsnr", "ongym_query_gsnr_many", "ongym_query_moves", "ongym_query_grid",
+    "ongym_masked_categorical_rows", "ongym_masked_categorical_backward_rows", "ongym_gae", "ongym_state_size", "ongym_state_save", "ongym_state_load", "ongym_fork", "ongym_query_available", "ongym_query_gsnr", "ongym_query_gsnr_many", "ongym_query_moves", "ongym_query_grid",
     "ongym_query_services", "ongym_query_request", "ongym_query_candidates", "ongym_query_path_free",
     "ongym_stats_get", "ongym_sync", "ongym_set_stream", "ongym_last_kernel_ms", "ongym_query_occupancy", "ongym_query_occupancy_policy",
     "ongym_last_error", "ongym_abi_version", "ongym_sizeof")

@@ -253,6 +253,114 @@ class BatchedQRMSAEnv:
                     "ongym_query_occupancy_policy")
         return dict(blocks_per_cu=nb.value, lds_bytes=lds.value, lean_kernel=bool(lean.value))
 
+    # ---- save / restore / fork replica states (ongym_state_*, ongym_fork; include/ongym.h) -----------------------------
+    # A replica's state is its network, running services, clock, pending request, request counter, stream key, parameters and
+    # ongym_stats, except the total_* work counters, which stay with the destination.  Python-side counters are not device
+    # state: rl.masked_categorical's draw counter (`_head_draws`) stays where it is.
+    def _state_replicas(self, replicas, distinct: bool):
+        """(count, int32 array or None) of a save / load replica list, checked before any library call."""
+        if replicas is None:
+            return self.batch_size, None
+        r = np.asarray(replicas)
+        if r.ndim != 1 or r.size < 1 or r.size > self.batch_size:
+            raise ValueError(f"replicas must be a 1-D list of 1..{self.batch_size} replica indices")
+        if not np.issubdtype(r.dtype, np.integer):
+            raise ValueError("replicas must be integers")
+        if r.min() < 0 or r.max() >= self.batch_size:
+            raise ValueError(f"replica indices must lie in [0, {self.batch_size})")
+        if distinct and len(np.unique(r)) != r.size:
+            raise ValueError("a load list must not repeat a replica")
+        return int(r.size), np.ascontiguousarray(r, np.int32)
+
+    def _state_flags(self, keep_stream: bool, keep_params: bool) -> int:
+        return (nat.STATE_KEEP_STREAM if keep_stream else 0) | (nat.STATE_KEEP_PARAMS if keep_params else 0)
+
+    def _check_blob(self, blob, nbytes: int, what: str, writable: bool):
+        if self.holder.struct.io_device:
+            import torch
+            from .. import rl
+            dev = rl._device(self)
+            if (not isinstance(blob, torch.Tensor) or blob.dtype != torch.uint8 or blob.dim() != 1 or blob.numel() != nbytes
+                    or not blob.is_contiguous() or blob.device != dev):
+                raise ValueError(f"{what} must be a contiguous 1-D uint8 tensor of {nbytes} bytes on {dev}")
+            if blob.data_ptr() % 16:
+                raise ValueError(f"{what} must be 16-byte aligned")
+            return C.c_void_p(blob.data_ptr())
+        if (not isinstance(blob, np.ndarray) or blob.dtype != np.uint8 or blob.ndim != 1 or blob.size != nbytes
+                or not blob.flags.c_contiguous or (writable and not blob.flags.writeable)):
+            raise ValueError(f"{what} must be a contiguous 1-D numpy uint8 array of {nbytes} bytes")
+        return C.c_void_p(blob.ctypes.data)
+
+    def _check_shared_stream(self):
+        if self.holder.struct.io_device:
+            from .. import rl
+            rl._check_stream(self)
+
+    def state_nbytes(self, count: Optional[int] = None) -> int:
+        """Bytes of a state blob of `count` replicas (None: all): a 256-byte header, then one block per replica."""
+        count = self.batch_size if count is None else int(count)
+        if not 1 <= count <= self.batch_size:
+            raise ValueError(f"count must lie in [1, {self.batch_size}]")
+        n = C.c_int64(0)
+        self._check(self.lib.ongym_state_size(self._h, count, C.byref(n)), "ongym_state_size")
+        return int(n.value)
+
+    def save_state(self, replicas=None, out=None):
+        """The states of `replicas` (host list of indices, None: all in order) as one blob: a numpy uint8 array, or with
+        io_device a uint8 tensor on the environment's device, written on torch's current stream without synchronising.
+        `out`: a blob of state_nbytes(len(replicas)) bytes to write instead of a new one."""
+        count, r = self._state_replicas(replicas, distinct=False)
+        nbytes = self.state_nbytes(count)
+        if out is None:
+            if self.holder.struct.io_device:
+                import torch
+                from .. import rl
+                out = torch.empty(nbytes, dtype=torch.uint8, device=rl._device(self))
+            else:
+                out = np.empty(nbytes, np.uint8)
+        ptr = self._check_blob(out, nbytes, "out", writable=True)
+        self._check_shared_stream()
+        self._check(self.lib.ongym_state_save(self._h, count, r.ctypes.data if r is not None else None, ptr),
+                    "ongym_state_save")
+        return out
+
+    def load_state(self, state, replicas=None, *, keep_stream: bool = False, keep_params: bool = False):
+        """Load a blob of save_state into `replicas` (host list of distinct indices, None: all in order).  The blob may come
+        from another environment of the same configuration (batch, device, launch power, margin and load may differ).
+        `keep_stream`: the replicas keep their own request streams; `keep_params`: their launch power, margin and load.
+        With io_device the header is read back first: that one small copy waits for the stream."""
+        count, r = self._state_replicas(replicas, distinct=True)
+        ptr = self._check_blob(state, self.state_nbytes(count), "state", writable=False)
+        self._check_shared_stream()
+        self._check(self.lib.ongym_state_load(self._h, count, r.ctypes.data if r is not None else None, ptr,
+                                              self._state_flags(keep_stream, keep_params)), "ongym_state_load")
+
+    def fork(self, src, *, keep_stream: bool = False, keep_params: bool = False):
+        """Replica j takes the pre-fork state of replica src[j] (any overlap: permutations, cycles, one into all); src[j] < 0 or
+        == j leaves replica j as it is.  `src`: int32 [batch], a numpy array, or with io_device an int32 tensor on the device
+        (then nothing synchronises, and entries >= batch leave their replica unchanged as well)."""
+        B = self.batch_size
+        flags = self._state_flags(keep_stream, keep_params)
+        if self.holder.struct.io_device:
+            import torch
+            from .. import rl
+            dev = rl._device(self)
+            if (not isinstance(src, torch.Tensor) or src.dtype != torch.int32 or tuple(src.shape) != (B,)
+                    or not src.is_contiguous() or src.device != dev):
+                raise ValueError(f"src must be a contiguous int32 [{B}] tensor on {dev}")
+            if src.data_ptr() % 4:
+                raise ValueError("src must be 4-byte aligned")
+            rl._check_stream(self)
+            self._check(self.lib.ongym_fork(self._h, C.c_void_p(src.data_ptr()), flags), "ongym_fork")
+            return
+        s = np.asarray(src)
+        if s.shape != (B,) or not np.issubdtype(s.dtype, np.integer):
+            raise ValueError(f"src must be an integer array of shape ({B},)")
+        if s.max() >= B or s.min() < -2 ** 31:
+            raise ValueError(f"src entries must lie in [-2^31, {B}) (negative: unchanged)")
+        s = np.ascontiguousarray(s, np.int32)
+        self._check(self.lib.ongym_fork(self._h, s.ctypes.data, flags), "ongym_fork")
+
     def set_stream(self, stream_handle: Optional[int]):
         """Run this environment's launches on the caller's HIP stream (e.g. torch.cuda.current_stream().cuda_stream); None
         returns to the environment's own stream.  See ongym_set_stream (include/ongym.h)."""
