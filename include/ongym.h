@@ -277,6 +277,27 @@ int ongym_policy_actions(ongym_env *env, int32_t policy, int32_t *actions, uint8
  * attenuation the interferer field is evaluated term by term (no pair table): same results, about ten times slower. */
 int ongym_observe(ongym_env *env, float *obs, uint8_t *mask);
 
+/* Block action space (DeepRMSA / optical-rl-gym; the reference's `blocks_to_consider` and get_available_blocks,
+ * qrmsa.pyx:231, 242, 1515-1531) for the CURRENT request of every replica, J = blocks in [1, 16], K = k_paths, M = n_mods:
+ * the fitting blocks of route k for n slots are the maximal free runs [a, a+L) of its row (the AND of its links' free bits),
+ * in increasing a, that hold a candidate of _get_candidates (qrmsa.pyx:515-541): L >= n for a run that ends at n_slots,
+ * L >= n + 1 (guard slot) otherwise.  Blocks(k, m) are the first J of them for n = get_number_slots(request, m).  Block
+ * action (k, j) decodes best format first, as first fit does (heuristics.py:923-966): the first m (M-1 down to 0) with a
+ * block Blocks(k, m)[j] = (a, L) whose calculate_osnr at (route k, slot a, n) passes minimum_osnr[m] + margin; none: invalid.
+ * So block action (k, 0) is first fit restricted to route k.
+ * obs        float32 [batch][3 + 3K + 6KJ]: ongym_observe's first 3 + K entries (bit rate, src, dst, K route lengths), then per
+ *            route its free-slot count / S and longest free run / S (-1: no such route), then per (k, j), route-major: valid,
+ *            a/S, L/S, n/S, (m+1)/M, (GSNR_dB - minimum_osnr[m] - margin)/10 (an invalid entry: 0, then five -1)
+ * mask       uint8   [batch][KJ + 1]: entry k*J + j = valid; the last entry (reject) is always 1
+ * action_map int32   [batch][KJ + 1]: the full action index k*M*S + (M-1-m)*S + a of every valid entry (get_action_index
+ *            with max_modulation_idx = M-1), the reject action K*M*S elsewhere: ongym_step_actions takes it as it is
+ * Read-only: no replica state, statistic or counter changes.  The QoT decisions are the step's own (same GN code, same n(m)), so
+ * a valid entry is always accepted.  A replica without a current request gets zeros in the first 3 + K entries and nothing
+ * valid.  Needs path_len_norm and max_bit_rate (not slot_bandwidth == channel_width*1e9: the GN model is the step's); refuses
+ * n_mods_consider < n_mods (no format window) with ONGYM_E_ARG.  Buffers: host buffers, or device buffers with cfg.io_device
+ * (then the call only launches on the environment's stream and nothing synchronises). */
+int ongym_observe_blocks(ongym_env *env, int32_t blocks, float *obs, uint8_t *mask, int32_t *action_map);
+
 /* One uniformly random VALID action per replica from an action mask [batch][k_paths*Mc*n_slots + 1] (as ongym_observe
  * writes it): what gymnasium's `action_space.sample(mask=info["mask"])` does on the reference's Discrete action space
  * (qrmsa.pyx:319-321; wrappers/qrmsa_gym.py:74-75 hands the mask out) - the masked random policy that exercises the

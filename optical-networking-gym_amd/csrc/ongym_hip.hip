@@ -22,6 +22,7 @@
 #include "ongym_policy_head.hpp"   // masked categorical action head (ongym_masked_categorical)
 #include "ongym_gae.hpp"           // GAE over a rollout (ongym_gae)
 #include "ongym_state.hpp"         // save / restore / fork of replica states (ongym_state_*, ongym_fork)
+#include "ongym_blocks.hpp"        // block action space: observation, mask and action map (ongym_observe_blocks)
 
 using namespace ongym;
 
@@ -1069,6 +1070,7 @@ void ongym_destroy(ongym_env *env) {
     if (env->d_out) (void)hipFree(env->d_out);
     if (env->h_pinned) (void)hipHostFree(env->h_pinned);
     if (env->d_state_stage) (void)hipFree(env->d_state_stage);
+    if (env->d_blocks) (void)hipFree(env->d_blocks);
     if (env->ev0) (void)hipEventDestroy(env->ev0);
     if (env->ev1) (void)hipEventDestroy(env->ev1);
     if (env->own_stream) (void)hipStreamDestroy(env->own_stream);      // a caller's stream (ongym_set_stream) is the caller's
@@ -1378,6 +1380,44 @@ int ongym_observe(ongym_env *env, float *obs, uint8_t *mask) {
     if (!env->cfg.io_device) {
         HIP_TRY(env, hipMemcpyAsync(obs, d_obs, B * obs_dim * sizeof(float), hipMemcpyDeviceToHost, env->stream));
         HIP_TRY(env, hipMemcpyAsync(mask, d_mask, B * nact, hipMemcpyDeviceToHost, env->stream));
+        HIP_TRY(env, hipStreamSynchronize(env->stream));
+    }
+    return ONGYM_OK;
+}
+
+int ongym_observe_blocks(ongym_env *env, int32_t blocks, float *obs, uint8_t *mask, int32_t *action_map) {
+    if (!env) return ONGYM_E_ARG;
+    if (!obs || !mask || !action_map) return fail_arg(env, "null obs/mask/action_map");
+    if (blocks < 1 || blocks > kMaxBlocks) return fail_arg(env, "blocks must lie in [1, 16]");
+    const Params &P = env->P;
+    if (P.n_mods_consider < P.n_mods)
+        return fail_arg(env, "the block action space has no format window: it needs modulations_to_consider == n_mods");
+    if (!P.path_len_norm || !(P.max_bit_rate > 0)) return fail_arg(env, "block observation needs path_len_norm and max_bit_rate = max(bit_rates)");
+    HIP_TRY(env, hipSetDevice(env->cfg.device));
+    const size_t B = (size_t)P.batch, J = (size_t)blocks, nout = (size_t)P.k_paths * J + 1;
+    const size_t obs_b = B * (size_t)blocks_obs_dim(P.k_paths, blocks) * sizeof(float), map_b = B * nout * sizeof(int32_t), mask_b = B * nout;
+    float *d_obs = obs; uint8_t *d_mask = mask; int32_t *d_map = action_map;
+    if (!env->cfg.io_device) {       // staging: obs | action_map | mask, grown on demand
+        const size_t o_map = (obs_b + 255) & ~(size_t)255, o_mask = (o_map + map_b + 255) & ~(size_t)255, total = o_mask + mask_b;
+        if (env->d_blocks_bytes < total) {
+            if (env->d_blocks) { (void)hipFree(env->d_blocks); env->d_blocks = nullptr; env->d_blocks_bytes = 0; }
+            HIP_TRY(env, hipMalloc(&env->d_blocks, total));
+            env->d_blocks_bytes = total;
+        }
+        char *base = static_cast<char *>(env->d_blocks);
+        d_obs = reinterpret_cast<float *>(base); d_map = reinterpret_cast<int32_t *>(base + o_map); d_mask = reinterpret_cast<uint8_t *>(base + o_mask);
+    }
+    HIP_TRY(env, hipEventRecord(env->ev0, env->stream));
+    const int rc = with_layout(P, [&](auto UA, auto R32) {   // the step kernels' (UA, R32): the same QoT decisions
+        return launch_lds(env, k_observe_blocks<UA, R32>, dim3(P.batch), blocks_lds_bytes(P), env->d_P, (int)blocks, d_obs, d_mask, d_map);
+    });
+    if (rc) return rc;
+    HIP_TRY(env, hipEventRecord(env->ev1, env->stream));
+    env->timed = true;
+    if (!env->cfg.io_device) {
+        HIP_TRY(env, hipMemcpyAsync(obs, d_obs, obs_b, hipMemcpyDeviceToHost, env->stream));
+        HIP_TRY(env, hipMemcpyAsync(mask, d_mask, mask_b, hipMemcpyDeviceToHost, env->stream));
+        HIP_TRY(env, hipMemcpyAsync(action_map, d_map, map_b, hipMemcpyDeviceToHost, env->stream));
         HIP_TRY(env, hipStreamSynchronize(env->stream));
     }
     return ONGYM_OK;

@@ -180,6 +180,64 @@ class BatchedQRMSAEnv:
         self._check(self.lib.ongym_observe(self._h, obs.ctypes.data, mask.ctypes.data), "ongym_observe")
         return obs, mask
 
+    # ---- block action space (ongym_observe_blocks, include/ongym.h) ------------------------------------------------------
+    def block_obs_dim(self, blocks: int) -> int:
+        k = self.holder.struct.k_paths
+        return 3 + 3 * k + 6 * k * int(blocks)
+
+    def observe_blocks(self, blocks: int, out=None):
+        """The block action space of the current requests (DeepRMSA / optical-rl-gym; the reference's `blocks_to_consider`):
+        (obs float32 [B, 3 + 3K + 6KJ], mask uint8 [B, KJ + 1], action_map int32 [B, KJ + 1]) for J = `blocks` in [1, 16].
+        Entry k*J + j is block j of route k, decoded best format first; the last entry is the reject action.  action_map holds
+        the full action index of every entry (the reject action where invalid): step(decode_block_actions(a, action_map)).
+        Read-only.  A host environment returns numpy arrays.  An io_device environment writes into `out` = (obs, mask,
+        action_map), torch tensors on its device, on torch's current stream (env.set_stream), without synchronising."""
+        J = int(blocks)
+        if not 1 <= J <= nat.MAX_BLOCKS:
+            raise ValueError(f"blocks must lie in [1, {nat.MAX_BLOCKS}]")
+        B, n = self.batch_size, self.holder.struct.k_paths * J + 1
+        shapes = ((B, self.block_obs_dim(J)), (B, n), (B, n))
+        if self.holder.struct.io_device:
+            import torch
+            from .. import rl
+            if out is None:
+                raise ValueError("an io_device environment needs out=(obs, mask, action_map) tensors")
+            if not isinstance(out, (tuple, list)) or len(out) != 3:
+                raise ValueError("out must be a tuple (obs, mask, action_map)")
+            dev = rl._device(self)
+            for t, name, dt, shape in zip(out, ("obs", "mask", "action_map"), (torch.float32, torch.uint8, torch.int32), shapes):
+                if (not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous()
+                        or t.device != dev):
+                    raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on {dev}")
+                if t.data_ptr() % 4:
+                    raise ValueError(f"{name} must be 4-byte aligned")
+            rl._check_stream(self)
+            self._check(self.lib.ongym_observe_blocks(self._h, J, *(C.c_void_p(t.data_ptr()) for t in out)),
+                        "ongym_observe_blocks")
+            return tuple(out)
+        if out is not None:
+            raise ValueError("out is for io_device environments; a host environment returns new arrays")
+        obs, mask, amap = np.zeros(shapes[0], np.float32), np.zeros(shapes[1], np.uint8), np.zeros(shapes[2], np.int32)
+        self._check(self.lib.ongym_observe_blocks(self._h, J, obs.ctypes.data, mask.ctypes.data, amap.ctypes.data),
+                    "ongym_observe_blocks")
+        return obs, mask, amap
+
+    @staticmethod
+    def decode_block_actions(block_actions, action_map):
+        """Full action indices [B] of block actions [B] through the action map of observe_blocks: one gather (numpy, or a torch
+        gather that stays on the map's device)."""
+        if isinstance(action_map, np.ndarray):
+            a = np.asarray(block_actions)
+            if a.shape != action_map.shape[:1] or not np.issubdtype(a.dtype, np.integer):
+                raise ValueError("block_actions must be integers, one per row of action_map")
+            if a.size and (a.min() < 0 or a.max() >= action_map.shape[1]):
+                raise ValueError(f"block actions must lie in [0, {action_map.shape[1]})")
+            return np.take_along_axis(action_map, a.astype(np.int64)[:, None], axis=1)[:, 0].astype(np.int32)
+        import torch
+        if not isinstance(block_actions, torch.Tensor) or block_actions.shape != action_map.shape[:1]:
+            raise ValueError("block_actions must be a tensor with one entry per row of action_map")
+        return torch.gather(action_map, 1, block_actions.to(device=action_map.device, dtype=torch.int64)[:, None])[:, 0]
+
     # ---- queries (plugin API) ----------------------------------------------------------------------------------------
     def available_slots(self, replica: int, path_id: int) -> np.ndarray:
         out = np.zeros(self.holder.struct.n_slots, np.int32)

@@ -1,0 +1,81 @@
+"""VecEnv-shaped batched environment over the block action space (DeepRMSA / optical-rl-gym; the reference's
+`blocks_to_consider`, envs/qrmsa.pyx:231, 242, and get_available_blocks, :1515-1531).
+
+The agent picks a route k and one of the first J free spectrum blocks j of that route that fit the request: action k*J + j,
+or K*J for reject.  The block is decoded best format first and placed at its start (BatchedQRMSAEnv.observe_blocks); the
+step itself is the environment's ordinary ongym_step_actions.  Conventions as QRMSAVecEnv (envs/vec_env.py):
+* `reset()` -> obs float32 [B, obs_dim], obs_dim = 3 + 3K + 6KJ
+* `step(block_actions)` -> (obs, rewards float32 [B], dones bool [B], infos list[dict]) with the `episode` snapshot of a
+  replica that terminated, and `qot_error` / `retry` flags (a masked agent never produces either)
+* `action_masks()` -> bool [B, n_actions], n_actions = K*J + 1
+"""
+from __future__ import annotations
+
+from typing import Sequence
+
+import numpy as np
+
+from .. import _native as nat
+from .batched import BatchedQRMSAEnv
+
+
+class QRMSABlockVecEnv:
+    def __init__(self, topology=None, *, num_envs: int, blocks_to_consider: int = 8, seed: int = 0, **kwargs):
+        kwargs.setdefault("auto_reset", True)
+        self.env = BatchedQRMSAEnv(topology, batch_size=num_envs, **kwargs)
+        c = self.env.holder.struct
+        if c.n_mods_consider < c.n_mods:
+            raise ValueError("the block action space has no format window: modulations_to_consider must cover every format")
+        self.blocks = int(blocks_to_consider)
+        if not 1 <= self.blocks <= nat.MAX_BLOCKS:
+            raise ValueError(f"blocks_to_consider must lie in [1, {nat.MAX_BLOCKS}]")
+        self.num_envs = int(num_envs)
+        self.obs_dim = self.env.block_obs_dim(self.blocks)
+        self.n_actions = c.k_paths * self.blocks + 1
+        self.env.seed(seed)
+        self._obs = self._mask = self._map = None
+
+    def _observe(self):
+        self._obs, mask, self._map = self.env.observe_blocks(self.blocks)
+        self._mask = mask.astype(bool)
+        return self._obs
+
+    def reset(self) -> np.ndarray:
+        self.env.reset()
+        return self._observe()
+
+    def action_masks(self) -> np.ndarray:
+        if self._mask is None:
+            self._observe()
+        return self._mask
+
+    def step(self, block_actions: Sequence[int]):
+        if self._map is None:
+            self._observe()
+        actions = self.env.decode_block_actions(np.asarray(block_actions, np.int64), self._map)
+        rec = self.env.step(actions)
+        rewards = rec["reward"].astype(np.float32)
+        qot = (rec["flags"] & nat.F_QOT_ERROR) != 0
+        rewards[qot] = -3.0
+        dones = rec["terminated"].astype(bool)
+        retry = rec["retry"] != 0
+        infos = [{} for _ in range(self.num_envs)]
+        if dones.any() or qot.any() or retry.any():
+            st = self.env.stats() if dones.any() else None
+            for i in np.flatnonzero(dones | qot | retry):
+                if qot[i]:
+                    infos[i]["qot_error"] = True
+                if retry[i]:
+                    infos[i]["retry"] = True
+                if dones[i]:
+                    s = st[i]
+                    infos[i]["episode"] = {
+                        "episode_service_blocking_rate": float(s["last_episode_service_blocking_rate"]),
+                        "episode_bit_rate_blocking_rate": float(s["last_episode_bit_rate_blocking_rate"]),
+                        "episode_services_accepted": int(s["last_episode_accepted"]),
+                        "mean_gsnr": float(s["last_mean_gsnr"]),
+                    }
+        return self._observe(), rewards, dones, infos
+
+    def close(self):
+        self.env.close()
