@@ -298,6 +298,29 @@ int ongym_observe(ongym_env *env, float *obs, uint8_t *mask);
  * (then the call only launches on the environment's stream and nothing synchronises). */
 int ongym_observe_blocks(ongym_env *env, int32_t blocks, float *obs, uint8_t *mask, int32_t *action_map);
 
+/* Spectrum fragmentation of every link of every replica (utils.pyx:61-107; qrmsa.pyx:1150-1186, 1353-1480), E = n_links in
+ * table order (link e = topology[u][v]["index"]), S = n_slots.  A free run is a maximal run of free slots of link e's row, a
+ * used run a maximal run of used slots; nothing at or above S counts.
+ * link_out    float32 [batch][E][8], computed in double and rounded once: F = free slots, free runs, Lmax = longest free run
+ *             (0: none), used runs, occupied span (one past the last used slot minus the first; 0: none), external
+ *             fragmentation 1 - Lmax/F (0 if F = 0), entropy -sum (L/S) ln(L/S) over the free runs L, rss sqrt(sum L^2) / sum L
+ *             (0 if F = 0).  The metrics of the utils functions on FREE runs, as their text says they measure: the reference's
+ *             heuristic_lowest_fragmentation hands them rows where 1 means free, so there they count used runs instead
+ *             (entry 3 is the per-link term of fragmentation_route_cuts as the reference computes it).
+ * compactness float64 [batch]: _get_network_compactness, (occupied / slot_hops) * (E / inner_free_blocks) summed over the links
+ *             with more than one used run (occupied = their spans, inner_free_blocks = free runs inside them; slot_hops = sum
+ *             of nslots * hops over the running services); 1.0 when no link has a free run inside its span.
+ * link_stats  float64 [batch][E][4] in/out (utilization, external_fragmentation, compactness, last_update), owned by the caller
+ *             and zeroed by it before the first call: _update_link_stats of every link at the replica's current_time, with the
+ *             reference's arithmetic and quirks (max_empty = 0 unless two or more free runs that are not exactly the first and
+ *             the last; the fragmentation divisor is the used-slot count, so an idle link gives NaN; the compactness divisor
+ *             counts used runs; utilization is not updated at current_time 0 but the other two are still divided by it).
+ *             NaN and negative values are kept.
+ * Any pointer may be NULL, not all three (ONGYM_E_ARG).  Read-only: no replica state, statistic or counter changes.  Buffers:
+ * host buffers (staged through a device buffer; the call synchronises), or device buffers with cfg.io_device (then the call
+ * only launches on the environment's stream and nothing synchronises). */
+int ongym_link_metrics(ongym_env *env, float *link_out, double *compactness, double *link_stats);
+
 /* One uniformly random VALID action per replica from an action mask [batch][k_paths*Mc*n_slots + 1] (as ongym_observe
  * writes it): what gymnasium's `action_space.sample(mask=info["mask"])` does on the reference's Discrete action space
  * (qrmsa.pyx:319-321; wrappers/qrmsa_gym.py:74-75 hands the mask out) - the masked random policy that exercises the

@@ -23,6 +23,7 @@
 #include "ongym_gae.hpp"           // GAE over a rollout (ongym_gae)
 #include "ongym_state.hpp"         // save / restore / fork of replica states (ongym_state_*, ongym_fork)
 #include "ongym_blocks.hpp"        // block action space: observation, mask and action map (ongym_observe_blocks)
+#include "ongym_metrics.hpp"       // per-link fragmentation metrics and link statistics (ongym_link_metrics)
 
 using namespace ongym;
 
@@ -1071,6 +1072,7 @@ void ongym_destroy(ongym_env *env) {
     if (env->h_pinned) (void)hipHostFree(env->h_pinned);
     if (env->d_state_stage) (void)hipFree(env->d_state_stage);
     if (env->d_blocks) (void)hipFree(env->d_blocks);
+    if (env->d_metrics) (void)hipFree(env->d_metrics);
     if (env->ev0) (void)hipEventDestroy(env->ev0);
     if (env->ev1) (void)hipEventDestroy(env->ev1);
     if (env->own_stream) (void)hipStreamDestroy(env->own_stream);      // a caller's stream (ongym_set_stream) is the caller's
@@ -1418,6 +1420,44 @@ int ongym_observe_blocks(ongym_env *env, int32_t blocks, float *obs, uint8_t *ma
         HIP_TRY(env, hipMemcpyAsync(obs, d_obs, obs_b, hipMemcpyDeviceToHost, env->stream));
         HIP_TRY(env, hipMemcpyAsync(mask, d_mask, mask_b, hipMemcpyDeviceToHost, env->stream));
         HIP_TRY(env, hipMemcpyAsync(action_map, d_map, map_b, hipMemcpyDeviceToHost, env->stream));
+        HIP_TRY(env, hipStreamSynchronize(env->stream));
+    }
+    return ONGYM_OK;
+}
+
+int ongym_link_metrics(ongym_env *env, float *link_out, double *compactness, double *link_stats) {
+    if (!env) return ONGYM_E_ARG;
+    if (!link_out && !compactness && !link_stats) return fail_arg(env, "null link_out/compactness/link_stats: nothing to compute");
+    const Params &P = env->P;
+    HIP_TRY(env, hipSetDevice(env->cfg.device));
+    const size_t B = (size_t)P.batch, E = (size_t)P.n_links;
+    const size_t out_b = link_out ? B * E * kLinkMetrics * sizeof(float) : 0, comp_b = compactness ? B * sizeof(double) : 0;
+    const size_t stats_b = link_stats ? B * E * kLinkStats * sizeof(double) : 0;
+    float *d_out = link_out; double *d_comp = compactness, *d_stats = link_stats;
+    if (!env->cfg.io_device) {       // staging: link_stats | compactness | link_out, grown on demand
+        const size_t o_comp = (stats_b + 255) & ~(size_t)255, o_out = (o_comp + comp_b + 255) & ~(size_t)255, total = o_out + out_b;
+        if (env->d_metrics_bytes < total) {
+            if (env->d_metrics) { (void)hipFree(env->d_metrics); env->d_metrics = nullptr; env->d_metrics_bytes = 0; }
+            HIP_TRY(env, hipMalloc(&env->d_metrics, total));
+            env->d_metrics_bytes = total;
+        }
+        char *base = static_cast<char *>(env->d_metrics);
+        d_stats = link_stats ? reinterpret_cast<double *>(base) : nullptr;
+        d_comp = compactness ? reinterpret_cast<double *>(base + o_comp) : nullptr;
+        d_out = link_out ? reinterpret_cast<float *>(base + o_out) : nullptr;
+        if (link_stats) HIP_TRY(env, hipMemcpyAsync(d_stats, link_stats, stats_b, hipMemcpyHostToDevice, env->stream));
+    }
+    HIP_TRY(env, hipEventRecord(env->ev0, env->stream));
+    const int rc = with_layout(P, [&](auto, auto R32) {     // the stored record codec
+        return launch_lds(env, k_link_metrics<R32>, dim3(P.batch), metrics_lds_bytes(P), env->d_P, d_out, d_comp, d_stats);
+    });
+    if (rc) return rc;
+    HIP_TRY(env, hipEventRecord(env->ev1, env->stream));
+    env->timed = true;
+    if (!env->cfg.io_device) {
+        if (link_out) HIP_TRY(env, hipMemcpyAsync(link_out, d_out, out_b, hipMemcpyDeviceToHost, env->stream));
+        if (compactness) HIP_TRY(env, hipMemcpyAsync(compactness, d_comp, comp_b, hipMemcpyDeviceToHost, env->stream));
+        if (link_stats) HIP_TRY(env, hipMemcpyAsync(link_stats, d_stats, stats_b, hipMemcpyDeviceToHost, env->stream));
         HIP_TRY(env, hipStreamSynchronize(env->stream));
     }
     return ONGYM_OK;

@@ -238,6 +238,50 @@ class BatchedQRMSAEnv:
             raise ValueError("block_actions must be a tensor with one entry per row of action_map")
         return torch.gather(action_map, 1, block_actions.to(device=action_map.device, dtype=torch.int64)[:, None])[:, 0]
 
+    # ---- link metrics (ongym_link_metrics, include/ongym.h) ----------------------------------------------------------------
+    def link_metrics(self, out=None, link_stats=None):
+        """Spectrum fragmentation of every link of every replica: (link float32 [B, E, 8], compactness float64 [B]), links in
+        table order, features nat.LINK_METRICS (on the free runs of each row), compactness = _get_network_compactness.
+        `link_stats` float64 [B, E, 4] (nat.LINK_STATS), zeroed by the caller before the first call, is updated in place as
+        _update_link_stats does for every link at each replica's current time.  Read-only.  A host environment returns numpy
+        arrays (link_stats: a C-contiguous numpy array).  An io_device environment writes into `out` = (link, compactness) and
+        link_stats, torch tensors on its device, on torch's current stream (env.set_stream), without synchronising."""
+        c = self.holder.struct
+        B, E = self.batch_size, c.n_links
+        shapes = ((B, E, len(nat.LINK_METRICS)), (B,), (B, E, len(nat.LINK_STATS)))
+        if c.io_device:
+            import torch
+            from .. import rl
+            if out is None:
+                raise ValueError("an io_device environment needs out=(link, compactness) tensors")
+            if not isinstance(out, (tuple, list)) or len(out) != 2:
+                raise ValueError("out must be a tuple (link, compactness)")
+            dev = rl._device(self)
+            named = list(zip(out, ("link", "compactness"), (torch.float32, torch.float64), shapes[:2]))
+            if link_stats is not None:
+                named.append((link_stats, "link_stats", torch.float64, shapes[2]))
+            for t, name, dt, shape in named:
+                if (not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous()
+                        or t.device != dev):
+                    raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on {dev}")
+                if t.data_ptr() % t.element_size():
+                    raise ValueError(f"{name} must be aligned to its element size")
+            rl._check_stream(self)
+            ptrs = [C.c_void_p(t.data_ptr()) for t in out] + [C.c_void_p(link_stats.data_ptr() if link_stats is not None else None)]
+            self._check(self.lib.ongym_link_metrics(self._h, *ptrs), "ongym_link_metrics")
+            return tuple(out)
+        if out is not None:
+            raise ValueError("out is for io_device environments; a host environment returns new arrays")
+        if link_stats is not None:
+            if (not isinstance(link_stats, np.ndarray) or link_stats.dtype != np.float64 or link_stats.shape != shapes[2]
+                    or not link_stats.flags.c_contiguous or not link_stats.flags.writeable):
+                raise ValueError(f"link_stats must be a writeable C-contiguous float64 numpy array of shape {shapes[2]}")
+        link, comp = np.zeros(shapes[0], np.float32), np.zeros(shapes[1], np.float64)
+        self._check(self.lib.ongym_link_metrics(self._h, link.ctypes.data, comp.ctypes.data,
+                                                link_stats.ctypes.data if link_stats is not None else None),
+                    "ongym_link_metrics")
+        return link, comp
+
     # ---- queries (plugin API) ----------------------------------------------------------------------------------------
     def available_slots(self, replica: int, path_id: int) -> np.ndarray:
         out = np.zeros(self.holder.struct.n_slots, np.int32)
