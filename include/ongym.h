@@ -321,6 +321,26 @@ int ongym_observe_blocks(ongym_env *env, int32_t blocks, float *obs, uint8_t *ma
  * only launches on the environment's stream and nothing synchronises). */
 int ongym_link_metrics(ongym_env *env, float *link_out, double *compactness, double *link_stats);
 
+/* Current quality of transmission of every running lightpath of every replica (core/osnr.pyx:21-142), C = capacity, E = n_links
+ * in table order.  Record i is the i-th record of the replica, in the order ongym_query_services returns them.  Each running
+ * service is evaluated at its own path, slot and slot count against every other running service of the replica, at the
+ * replica's current launch power; itself is skipped, and with id tracking every running service with its service_id too
+ * (quirk Q12, core/osnr.pyx:65), as measure_disruptions and defragmentation evaluate running services.  Any attenuation.
+ * svc_out     float64 [batch][C][4]: GSNR, ASE, NLI (dB) and the margin GSNR - mod_min_osnr[modulation] of record i < active;
+ *             NaN for the records at and beyond active.
+ * replica_out float64 [batch][6]: running services; services below minimum_osnr (no margin: measure_disruptions' test,
+ *             qrmsa.pyx:947); services below minimum_osnr + margin (the replica's margin: those the step's QoT check would
+ *             refuse now); the lowest margin (NaN if nothing runs); the mean GSNR in dB (NaN if nothing runs); the record index of
+ *             the lowest margin (the lowest index on a tie, -1 if nothing runs).  Both "below" tests compare in the linear domain
+ *             with the dB fallback band of the step's QoT check, so they decide as the step decides.
+ * link_out    float32 [batch][E][3]: running lightpaths that cross the link, their lowest margin (NaN if none), how many of
+ *             them are below minimum_osnr.
+ * Any pointer may be NULL, not all three (ONGYM_E_ARG).  Read-only: no replica state, statistic, counter (total_gn_evals
+ * included), disrupted flag or random-number position changes.  Buffers: host buffers (staged through a device buffer grown on
+ * demand; the call synchronises), or device buffers with cfg.io_device (then the call only launches on the environment's
+ * stream and nothing synchronises).  ongym_last_kernel_ms times the kernel. */
+int ongym_service_qot(ongym_env *env, double *svc_out, double *replica_out, float *link_out);
+
 /* One uniformly random VALID action per replica from an action mask [batch][k_paths*Mc*n_slots + 1] (as ongym_observe
  * writes it): what gymnasium's `action_space.sample(mask=info["mask"])` does on the reference's Discrete action space
  * (qrmsa.pyx:319-321; wrappers/qrmsa_gym.py:74-75 hands the mask out) - the masked random policy that exercises the

@@ -482,9 +482,10 @@ __device__ __forceinline__ void mark_mask(Ctx &c, uint32_t mask, int lo, int hi,
 }
 
 // ---- GN model (core/osnr.pyx:21-142) ----------------------------------------------------------------------------
-// pass 1: compact the indices of the running services that share >= 1 link with the candidate path.
-template <bool R32>
-__device__ __forceinline__ int gn_build_list(Ctx &c, uint64_t cm0, uint64_t cm1) {
+// pass 1: compact the indices of the running services that share >= 1 link with the candidate path.  EXCL: record `excl` is
+// left out too (a running service evaluated against the others, ongym_qot.hpp).
+template <bool R32, bool EXCL = false>
+__device__ __forceinline__ int gn_build_list(Ctx &c, uint64_t cm0, uint64_t cm1, int excl = -1) {
     const Params &P = c.P;
     int L = 0;
     // two chunks of 64 records per iteration: both LDS reads (and, in the generic codec, both mask gathers) are in flight
@@ -502,6 +503,7 @@ __device__ __forceinline__ int gn_build_list(Ctx &c, uint64_t cm0, uint64_t cm1)
             if (i0 < c.active && c.sq[i0] == (uint32_t)c.skip_id) ov0 = false;
             if (i1 < c.active && c.sq[i1] == (uint32_t)c.skip_id) ov1 = false;
         }
+        if (EXCL) { if (i0 == excl) ov0 = false; if (i1 == excl) ov1 = false; }
         const uint64_t bal0 = __ballot(ov0), bal1 = __ballot(ov1);
         const int n0 = __popcll((unsigned long long)bal0);
         if (ov0) c.list[L + __popcll((unsigned long long)(bal0 & lanes_below(c.lane)))] = (uint16_t)i0;

@@ -24,6 +24,7 @@
 #include "ongym_state.hpp"         // save / restore / fork of replica states (ongym_state_*, ongym_fork)
 #include "ongym_blocks.hpp"        // block action space: observation, mask and action map (ongym_observe_blocks)
 #include "ongym_metrics.hpp"       // per-link fragmentation metrics and link statistics (ongym_link_metrics)
+#include "ongym_qot.hpp"           // current QoT of every running lightpath (ongym_service_qot)
 
 using namespace ongym;
 
@@ -1073,6 +1074,7 @@ void ongym_destroy(ongym_env *env) {
     if (env->d_state_stage) (void)hipFree(env->d_state_stage);
     if (env->d_blocks) (void)hipFree(env->d_blocks);
     if (env->d_metrics) (void)hipFree(env->d_metrics);
+    if (env->d_qot) (void)hipFree(env->d_qot);
     if (env->ev0) (void)hipEventDestroy(env->ev0);
     if (env->ev1) (void)hipEventDestroy(env->ev1);
     if (env->own_stream) (void)hipStreamDestroy(env->own_stream);      // a caller's stream (ongym_set_stream) is the caller's
@@ -1458,6 +1460,46 @@ int ongym_link_metrics(ongym_env *env, float *link_out, double *compactness, dou
         if (link_out) HIP_TRY(env, hipMemcpyAsync(link_out, d_out, out_b, hipMemcpyDeviceToHost, env->stream));
         if (compactness) HIP_TRY(env, hipMemcpyAsync(compactness, d_comp, comp_b, hipMemcpyDeviceToHost, env->stream));
         if (link_stats) HIP_TRY(env, hipMemcpyAsync(link_stats, d_stats, stats_b, hipMemcpyDeviceToHost, env->stream));
+        HIP_TRY(env, hipStreamSynchronize(env->stream));
+    }
+    return ONGYM_OK;
+}
+
+int ongym_service_qot(ongym_env *env, double *svc_out, double *replica_out, float *link_out) {
+    if (!env) return ONGYM_E_ARG;
+    if (!svc_out && !replica_out && !link_out) return fail_arg(env, "null svc_out/replica_out/link_out: nothing to compute");
+    const Params &P = env->P;
+    const size_t lds = qot_lds_bytes(P);
+    if (lds > 160 * 1024) return fail_arg(env, "the QoT kernel's LDS block exceeds 160 KiB: lower capacity", ONGYM_E_LIMIT);
+    HIP_TRY(env, hipSetDevice(env->cfg.device));
+    const size_t B = (size_t)P.batch;
+    const size_t svc_b = svc_out ? B * P.capacity * kServiceQot * sizeof(double) : 0;
+    const size_t rep_b = replica_out ? B * kReplicaQot * sizeof(double) : 0;
+    const size_t link_b = link_out ? B * P.n_links * kLinkQot * sizeof(float) : 0;
+    double *d_svc = svc_out, *d_rep = replica_out; float *d_link = link_out;
+    if (!env->cfg.io_device) {       // staging: svc_out | replica_out | link_out, grown on demand
+        const size_t o_rep = (svc_b + 255) & ~(size_t)255, o_link = (o_rep + rep_b + 255) & ~(size_t)255, total = o_link + link_b;
+        if (env->d_qot_bytes < total) {
+            if (env->d_qot) { (void)hipFree(env->d_qot); env->d_qot = nullptr; env->d_qot_bytes = 0; }
+            HIP_TRY(env, hipMalloc(&env->d_qot, total));
+            env->d_qot_bytes = total;
+        }
+        char *base = static_cast<char *>(env->d_qot);
+        d_svc = svc_out ? reinterpret_cast<double *>(base) : nullptr;
+        d_rep = replica_out ? reinterpret_cast<double *>(base + o_rep) : nullptr;
+        d_link = link_out ? reinterpret_cast<float *>(base + o_link) : nullptr;
+    }
+    HIP_TRY(env, hipEventRecord(env->ev0, env->stream));
+    const int rc = with_layout(P, [&](auto UA, auto R32) {     // attenuation and the stored record codec
+        return launch_lds(env, k_service_qot<UA, R32>, dim3(P.batch), lds, env->d_P, d_svc, d_rep, d_link);
+    });
+    if (rc) return rc;
+    HIP_TRY(env, hipEventRecord(env->ev1, env->stream));
+    env->timed = true;
+    if (!env->cfg.io_device) {
+        if (svc_out) HIP_TRY(env, hipMemcpyAsync(svc_out, d_svc, svc_b, hipMemcpyDeviceToHost, env->stream));
+        if (replica_out) HIP_TRY(env, hipMemcpyAsync(replica_out, d_rep, rep_b, hipMemcpyDeviceToHost, env->stream));
+        if (link_out) HIP_TRY(env, hipMemcpyAsync(link_out, d_link, link_b, hipMemcpyDeviceToHost, env->stream));
         HIP_TRY(env, hipStreamSynchronize(env->stream));
     }
     return ONGYM_OK;

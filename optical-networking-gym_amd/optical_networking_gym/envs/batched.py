@@ -282,6 +282,46 @@ class BatchedQRMSAEnv:
                     "ongym_link_metrics")
         return link, comp
 
+    # ---- QoT of the running lightpaths (ongym_service_qot, include/ongym.h) ------------------------------------------------
+    def service_qot(self, out=None):
+        """Current GSNR of every running lightpath of every replica, each against all the others at the replica's launch power:
+        (svc float64 [B, C, 4], replica float64 [B, 6], link float32 [B, E, 3]).  svc: nat.SERVICE_QOT (GSNR, ASE, NLI in dB,
+        margin) of record i (the order of services()), NaN at and beyond the running count; replica: nat.REPLICA_QOT; link:
+        nat.LINK_QOT, links in table order.  Read-only.  A host environment returns numpy arrays.  An io_device environment
+        writes into `out` = (svc, replica, link), torch tensors on its device (any of them None: not computed, not all three),
+        on torch's current stream (env.set_stream), without synchronising."""
+        c = self.holder.struct
+        B = self.batch_size
+        shapes = ((B, c.capacity, len(nat.SERVICE_QOT)), (B, len(nat.REPLICA_QOT)), (B, c.n_links, len(nat.LINK_QOT)))
+        if c.io_device:
+            import torch
+            from .. import rl
+            if out is None:
+                raise ValueError("an io_device environment needs out=(svc, replica, link) tensors")
+            if not isinstance(out, (tuple, list)) or len(out) != 3:
+                raise ValueError("out must be a tuple (svc, replica, link)")
+            if all(t is None for t in out):
+                raise ValueError("out: at least one of svc, replica, link must be a tensor")
+            dev = rl._device(self)
+            for t, name, dt, shape in zip(out, ("svc", "replica", "link"), (torch.float64, torch.float64, torch.float32), shapes):
+                if t is None:
+                    continue
+                if (not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous()
+                        or t.device != dev):
+                    raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on {dev}")
+                if t.data_ptr() % t.element_size():
+                    raise ValueError(f"{name} must be aligned to its element size")
+            rl._check_stream(self)
+            ptrs = [C.c_void_p(t.data_ptr() if t is not None else None) for t in out]
+            self._check(self.lib.ongym_service_qot(self._h, *ptrs), "ongym_service_qot")
+            return tuple(out)
+        if out is not None:
+            raise ValueError("out is for io_device environments; a host environment returns new arrays")
+        svc, rep, link = np.zeros(shapes[0], np.float64), np.zeros(shapes[1], np.float64), np.zeros(shapes[2], np.float32)
+        self._check(self.lib.ongym_service_qot(self._h, svc.ctypes.data, rep.ctypes.data, link.ctypes.data),
+                    "ongym_service_qot")
+        return svc, rep, link
+
     # ---- queries (plugin API) ----------------------------------------------------------------------------------------
     def available_slots(self, replica: int, path_id: int) -> np.ndarray:
         out = np.zeros(self.holder.struct.n_slots, np.int32)
