@@ -341,6 +341,36 @@ int ongym_link_metrics(ongym_env *env, float *link_out, double *compactness, dou
  * stream and nothing synchronises).  ongym_last_kernel_ms times the kernel. */
 int ongym_service_qot(ongym_env *env, double *svc_out, double *replica_out, float *link_out);
 
+/* What each candidate action would do to the lightpaths that are running, before it is taken (A = n_actions, C = capacity).
+ * actions [batch][A] are full step action indices (a row of ongym_observe_blocks' action_map, ongym_policy_actions' output
+ * with A = 1, or any list), 1 <= A <= 256.  Each is decoded exactly as ongym_step_actions decodes it for the replica's current
+ * request (route, format, start slot, the slot count of the step's own per-request table).  The candidate is that lightpath at
+ * the replica's current launch power; its victims are the running records that share at least one link with its route (with id
+ * tracking, records with the current request's service_id are not: quirk Q12).  Per victim, "before" is its current linear
+ * ASE + NLI exactly as ongym_service_qot reports it, and "after" adds the candidate as one more interferer on every shared
+ * link (the GN model is additive in the interferers, core/osnr.pyx:64-93): calculate_osnr(victim) inside
+ * measure_disruptions right after the provisioning and before any departure (envs/qrmsa.pyx:937-953).  The candidate's own
+ * QoT is not evaluated (the action mask says so already).
+ * impact_out float64 [batch][A][8]:
+ *   0 status                0 evaluated; 1 skipped (index < 0, the reject action or beyond it, or no current request);
+ *                           2 spectrum not free (the step's is_path_free fails, or no such route / format / slot count)
+ *   1 affected              number of victims
+ *   2 below_minimum_after   victims with GSNR_after < minimum_osnr of their format (the test of qrmsa.pyx:947)
+ *   3 newly_below_minimum   of those, the ones not below before
+ *   4 newly_below_margin    victims below minimum_osnr + the replica's margin after and not before
+ *   5 lowest_margin_after   min over the victims of GSNR_after - minimum_osnr (dB)
+ *   6 largest_drop          max over the victims of GSNR_before - GSNR_after (dB)
+ *   7 lowest_margin_record  record index of column 5 (the lowest index on a tie; the order of ongym_query_services)
+ *   Status 1 or 2: columns 1-7 are NaN.  Status 0 without a victim: columns 1-4 are 0, 5 and 6 NaN, 7 is -1.  Every "below"
+ *   decision compares linear 1/GSNR inside the 1e-9 dB-fallback band of the step's QoT check and of ongym_service_qot.
+ * svc_in      NULL, or the svc_out (float64 [batch][C][4], dB) of an ongym_service_qot call on the SAME state: "before" is then
+ *             10^(-ASE/10) + 10^(-NLI/10) of it and the kernel evaluates no baseline of its own.
+ * Read-only: no replica state, statistic, counter (total_gn_evals included), disrupted flag or random-number position changes.
+ * Buffers: host buffers (staged through a device buffer grown on demand; the call synchronises), or device buffers with
+ * cfg.io_device (then the call only launches on the environment's stream and nothing synchronises).  ongym_last_kernel_ms
+ * times the kernel. */
+int ongym_action_impact(ongym_env *env, int32_t n_actions, const int32_t *actions, const double *svc_in, double *impact_out);
+
 /* One uniformly random VALID action per replica from an action mask [batch][k_paths*Mc*n_slots + 1] (as ongym_observe
  * writes it): what gymnasium's `action_space.sample(mask=info["mask"])` does on the reference's Discrete action space
  * (qrmsa.pyx:319-321; wrappers/qrmsa_gym.py:74-75 hands the mask out) - the masked random policy that exercises the

@@ -25,6 +25,7 @@
 #include "ongym_blocks.hpp"        // block action space: observation, mask and action map (ongym_observe_blocks)
 #include "ongym_metrics.hpp"       // per-link fragmentation metrics and link statistics (ongym_link_metrics)
 #include "ongym_qot.hpp"           // current QoT of every running lightpath (ongym_service_qot)
+#include "ongym_impact.hpp"        // effect of candidate actions on the running lightpaths (ongym_action_impact)
 
 using namespace ongym;
 
@@ -1075,6 +1076,7 @@ void ongym_destroy(ongym_env *env) {
     if (env->d_blocks) (void)hipFree(env->d_blocks);
     if (env->d_metrics) (void)hipFree(env->d_metrics);
     if (env->d_qot) (void)hipFree(env->d_qot);
+    if (env->d_impact) (void)hipFree(env->d_impact);
     if (env->ev0) (void)hipEventDestroy(env->ev0);
     if (env->ev1) (void)hipEventDestroy(env->ev1);
     if (env->own_stream) (void)hipStreamDestroy(env->own_stream);      // a caller's stream (ongym_set_stream) is the caller's
@@ -1500,6 +1502,48 @@ int ongym_service_qot(ongym_env *env, double *svc_out, double *replica_out, floa
         if (svc_out) HIP_TRY(env, hipMemcpyAsync(svc_out, d_svc, svc_b, hipMemcpyDeviceToHost, env->stream));
         if (replica_out) HIP_TRY(env, hipMemcpyAsync(replica_out, d_rep, rep_b, hipMemcpyDeviceToHost, env->stream));
         if (link_out) HIP_TRY(env, hipMemcpyAsync(link_out, d_link, link_b, hipMemcpyDeviceToHost, env->stream));
+        HIP_TRY(env, hipStreamSynchronize(env->stream));
+    }
+    return ONGYM_OK;
+}
+
+int ongym_action_impact(ongym_env *env, int32_t n_actions, const int32_t *actions, const double *svc_in, double *impact_out) {
+    if (!env) return ONGYM_E_ARG;
+    if (!actions || !impact_out) return fail_arg(env, "null actions/impact_out");
+    if (n_actions < 1 || n_actions > kMaxImpactActions) return fail_arg(env, "n_actions must lie in [1, 256]");
+    const Params &P = env->P;
+    const size_t lds = impact_lds_bytes(P);
+    if (lds > 160 * 1024) return fail_arg(env, "the impact kernel's LDS block exceeds 160 KiB: lower capacity", ONGYM_E_LIMIT);
+    HIP_TRY(env, hipSetDevice(env->cfg.device));
+    const size_t B = (size_t)P.batch, A = (size_t)n_actions;
+    const size_t act_b = B * A * sizeof(int32_t), out_b = B * A * kActionImpact * sizeof(double);
+    const size_t svc_b = svc_in ? B * P.capacity * kServiceQot * sizeof(double) : 0;
+    const int32_t *d_act = actions; const double *d_svc = svc_in; double *d_out = impact_out;
+    if (!env->cfg.io_device) {       // staging: impact_out | svc_in | actions, grown on demand
+        const size_t o_svc = (out_b + 255) & ~(size_t)255, o_act = (o_svc + svc_b + 255) & ~(size_t)255, total = o_act + act_b;
+        if (env->d_impact_bytes < total) {
+            if (env->d_impact) { (void)hipFree(env->d_impact); env->d_impact = nullptr; env->d_impact_bytes = 0; }
+            HIP_TRY(env, hipMalloc(&env->d_impact, total));
+            env->d_impact_bytes = total;
+        }
+        char *base = static_cast<char *>(env->d_impact);
+        d_out = reinterpret_cast<double *>(base);
+        HIP_TRY(env, hipMemcpyAsync(base + o_act, actions, act_b, hipMemcpyHostToDevice, env->stream));
+        d_act = reinterpret_cast<const int32_t *>(base + o_act);
+        if (svc_in) {
+            HIP_TRY(env, hipMemcpyAsync(base + o_svc, svc_in, svc_b, hipMemcpyHostToDevice, env->stream));
+            d_svc = reinterpret_cast<const double *>(base + o_svc);
+        }
+    }
+    HIP_TRY(env, hipEventRecord(env->ev0, env->stream));
+    const int rc = with_layout(P, [&](auto UA, auto R32) {     // attenuation and the stored record codec
+        return launch_lds(env, k_action_impact<UA, R32>, dim3(P.batch), lds, env->d_P, (int)n_actions, d_act, d_svc, d_out);
+    });
+    if (rc) return rc;
+    HIP_TRY(env, hipEventRecord(env->ev1, env->stream));
+    env->timed = true;
+    if (!env->cfg.io_device) {
+        HIP_TRY(env, hipMemcpyAsync(impact_out, d_out, out_b, hipMemcpyDeviceToHost, env->stream));
         HIP_TRY(env, hipStreamSynchronize(env->stream));
     }
     return ONGYM_OK;

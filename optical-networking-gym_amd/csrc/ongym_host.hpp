@@ -28,6 +28,7 @@ struct ongym_env {
     void *d_blocks = nullptr; size_t d_blocks_bytes = 0;    // staging of ongym_observe_blocks with host buffers (grown on demand)
     void *d_metrics = nullptr; size_t d_metrics_bytes = 0;  // staging of ongym_link_metrics with host buffers (grown on demand)
     void *d_qot = nullptr; size_t d_qot_bytes = 0;          // staging of ongym_service_qot with host buffers (grown on demand)
+    void *d_impact = nullptr; size_t d_impact_bytes = 0;    // staging of ongym_action_impact with host buffers (grown on demand)
     int32_t *d_scratch_i = nullptr; size_t scratch_i_bytes = 0; double *d_scratch_d = nullptr;
     void *h_pinned = nullptr; size_t h_pinned_bytes = 0;     // pinned staging of ongym_step_actions_bundle
     bool has_source = false;

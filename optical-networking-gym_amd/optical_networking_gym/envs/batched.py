@@ -322,6 +322,69 @@ class BatchedQRMSAEnv:
                     "ongym_service_qot")
         return svc, rep, link
 
+    # ---- effect of candidate actions on the running lightpaths (ongym_action_impact, include/ongym.h) -----------------------
+    def action_impact(self, actions, svc=None, out=None):
+        """What each candidate action would do to the running lightpaths: float64 [B, A, 8], columns nat.ACTION_IMPACT (status,
+        victims, victims below minimum_osnr after, newly below it, newly below minimum_osnr + margin, lowest margin after,
+        largest GSNR drop, record of the lowest margin), for int32 actions [B, A] (or [B]: A = 1) of full step action indices,
+        1 <= A <= nat.MAX_IMPACT_ACTIONS.  svc: optionally the svc array of service_qot() on the same state, which saves the
+        baseline pass.  Read-only.  A host environment takes and returns numpy arrays.  An io_device environment takes torch
+        tensors on its device and writes into `out`, on torch's current stream (env.set_stream), without synchronising."""
+        c = self.holder.struct
+        B = self.batch_size
+        svc_shape = (B, c.capacity, len(nat.SERVICE_QOT))
+        if c.io_device:
+            import torch
+            from .. import rl
+            dev = rl._device(self)
+            if not isinstance(actions, torch.Tensor) or actions.dtype != torch.int32 or actions.device != dev:
+                raise ValueError(f"actions must be a torch.int32 tensor on {dev}")
+            if actions.dim() == 1:
+                actions = actions.reshape(-1, 1)
+            if actions.dim() != 2 or actions.shape[0] != B or not actions.is_contiguous():
+                raise ValueError(f"actions must be contiguous with shape ({B}, A) or ({B},)")
+            A = int(actions.shape[1])
+            if not 1 <= A <= nat.MAX_IMPACT_ACTIONS:
+                raise ValueError(f"the number of actions per replica must lie in [1, {nat.MAX_IMPACT_ACTIONS}]")
+            if out is None:
+                raise ValueError("an io_device environment needs out, a float64 tensor of shape (B, A, 8)")
+            shape = (B, A, len(nat.ACTION_IMPACT))
+            for t, name, sh in ((out, "out", shape), (svc, "svc", svc_shape)):
+                if t is None:
+                    continue
+                if (not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or tuple(t.shape) != sh or not t.is_contiguous()
+                        or t.device != dev):
+                    raise ValueError(f"{name} must be a contiguous torch.float64 tensor of shape {sh} on {dev}")
+                if t.data_ptr() % t.element_size():
+                    raise ValueError(f"{name} must be aligned to its element size")
+            if actions.data_ptr() % 4:
+                raise ValueError("actions must be aligned to its element size")
+            rl._check_stream(self)
+            self._check(self.lib.ongym_action_impact(self._h, A, C.c_void_p(actions.data_ptr()),
+                                                     C.c_void_p(svc.data_ptr() if svc is not None else None),
+                                                     C.c_void_p(out.data_ptr())), "ongym_action_impact")
+            return out
+        if out is not None:
+            raise ValueError("out is for io_device environments; a host environment returns a new array")
+        if not isinstance(actions, np.ndarray) or actions.dtype != np.int32:
+            raise ValueError("actions must be a numpy int32 array")
+        if actions.ndim == 1:
+            actions = actions.reshape(-1, 1)
+        if actions.ndim != 2 or actions.shape[0] != B:
+            raise ValueError(f"actions must have shape ({B}, A) or ({B},)")
+        A = int(actions.shape[1])
+        if not 1 <= A <= nat.MAX_IMPACT_ACTIONS:
+            raise ValueError(f"the number of actions per replica must lie in [1, {nat.MAX_IMPACT_ACTIONS}]")
+        actions = np.ascontiguousarray(actions)
+        if svc is not None:
+            if not isinstance(svc, np.ndarray) or svc.dtype != np.float64 or svc.shape != svc_shape:
+                raise ValueError(f"svc must be a numpy float64 array of shape {svc_shape}")
+            svc = np.ascontiguousarray(svc)
+        res = np.zeros((B, A, len(nat.ACTION_IMPACT)), np.float64)
+        self._check(self.lib.ongym_action_impact(self._h, A, actions.ctypes.data, svc.ctypes.data if svc is not None else None,
+                                                 res.ctypes.data), "ongym_action_impact")
+        return res
+
     # ---- queries (plugin API) ----------------------------------------------------------------------------------------
     def available_slots(self, replica: int, path_id: int) -> np.ndarray:
         out = np.zeros(self.holder.struct.n_slots, np.int32)

@@ -8,6 +8,9 @@ step itself is the environment's ordinary ongym_step_actions.  Conventions as QR
 * `step(block_actions)` -> (obs, rewards float32 [B], dones bool [B], infos list[dict]) with the `episode` snapshot of a
   replica that terminated, and `qot_error` / `retry` flags (a masked agent never produces either)
 * `action_masks()` -> bool [B, n_actions], n_actions = K*J + 1
+* `protect_running=True`: `action_masks()` also clears every block action that would push a running lightpath that is not below
+  its format's minimum_osnr now below it (BatchedQRMSAEnv.action_impact, column newly_below_minimum; reject stays allowed), and
+  every info dict of `step` carries `disrupts`, that count for the action taken.  Default False: nothing changes.
 """
 from __future__ import annotations
 
@@ -20,7 +23,8 @@ from .batched import BatchedQRMSAEnv
 
 
 class QRMSABlockVecEnv:
-    def __init__(self, topology=None, *, num_envs: int, blocks_to_consider: int = 8, seed: int = 0, **kwargs):
+    def __init__(self, topology=None, *, num_envs: int, blocks_to_consider: int = 8, seed: int = 0,
+                 protect_running: bool = False, **kwargs):
         kwargs.setdefault("auto_reset", True)
         self.env = BatchedQRMSAEnv(topology, batch_size=num_envs, **kwargs)
         c = self.env.holder.struct
@@ -33,11 +37,16 @@ class QRMSABlockVecEnv:
         self.obs_dim = self.env.block_obs_dim(self.blocks)
         self.n_actions = c.k_paths * self.blocks + 1
         self.env.seed(seed)
-        self._obs = self._mask = self._map = None
+        self.protect_running = bool(protect_running)
+        self._obs = self._mask = self._map = self._newly = None
 
     def _observe(self):
         self._obs, mask, self._map = self.env.observe_blocks(self.blocks)
         self._mask = mask.astype(bool)
+        if self.protect_running:
+            newly = self.env.action_impact(self._map)[:, :, nat.ACTION_IMPACT.index("newly_below_minimum")]
+            self._newly = np.nan_to_num(newly, nan=0.0).astype(np.int64)      # NaN: reject, or a block that is masked anyway
+            self._mask &= self._newly == 0
         return self._obs
 
     def reset(self) -> np.ndarray:
@@ -52,14 +61,16 @@ class QRMSABlockVecEnv:
     def step(self, block_actions: Sequence[int]):
         if self._map is None:
             self._observe()
-        actions = self.env.decode_block_actions(np.asarray(block_actions, np.int64), self._map)
+        block_actions = np.asarray(block_actions, np.int64)
+        actions = self.env.decode_block_actions(block_actions, self._map)
+        disrupts = self._newly[np.arange(self.num_envs), block_actions] if self.protect_running else None
         rec = self.env.step(actions)
         rewards = rec["reward"].astype(np.float32)
         qot = (rec["flags"] & nat.F_QOT_ERROR) != 0
         rewards[qot] = -3.0
         dones = rec["terminated"].astype(bool)
         retry = rec["retry"] != 0
-        infos = [{} for _ in range(self.num_envs)]
+        infos = [{} for _ in range(self.num_envs)] if disrupts is None else [{"disrupts": int(d)} for d in disrupts]
         if dones.any() or qot.any() or retry.any():
             st = self.env.stats() if dones.any() else None
             for i in np.flatnonzero(dones | qot | retry):

@@ -572,6 +572,13 @@ class QRMSAEnv:
         """heuristic_shortest_available_path_first_fit_best_modulation (heuristics.py:923-966) on device."""
         return self.policy_action(nat.POLICY_FIRST_FIT)
 
+    def action_impact(self, action: int) -> dict:
+        """What `step(action)` would do to the running lightpaths, before it is taken (BatchedQRMSAEnv.action_impact): a dict
+        with the keys of nat.ACTION_IMPACT; the counts, the status and the record index are ints where they are defined."""
+        row = self._dev.action_impact(np.array([[int(action)]], np.int32))[0, 0]
+        whole = ("status", "affected", "below_minimum_after", "newly_below_minimum", "newly_below_margin", "lowest_margin_record")
+        return {k: (int(v) if k in whole and not np.isnan(v) else float(v)) for k, v in zip(nat.ACTION_IMPACT, row)}
+
     def close(self):
         if self.file_stats is not None:
             self.file_stats.close()
