@@ -30,8 +30,10 @@
 //   * the units are compiled with -mllvm -disable-machine-licm (__graft_entry__.FAST_UNIT_FLAGS): hoisting the constants of cold
 //     code out of the step loop cost 53 spilled SGPRs + 13 spilled VGPRs; and wave-uniform values that must stay in a scalar
 //     register across the loop are pinned by hand (ep_len).  Round 3 measured that this kernel pays per ISSUED INSTRUCTION
-//     (~0.3 % per scalar instruction on the per-request path) and not per hidden latency: hence s_bitset0 / s_bfm_b64 /
-//     v_mad_u32_u24 / ds_write2_b32 in place of the generic sequences, counters derived at store time, and vz.
+//     (~0.3 % per scalar instruction on the per-request path): hence s_bitset0 / s_bfm_b64 / v_mad_u32_u24 / ds_write2_b32 in
+//     place of the generic sequences, counters derived at store time, and vz.  Hiding latency pays only where it costs no
+//     instruction and no register: independent LDS reads issued together (path_and, the cache chain, departures) and the first
+//     evaluation's table gathers issued before the link weights are summed (build_cache) - DESIGN.md section 4.
 // The state in HBM is the generic kernels' (same arrays, same record codec), converted on load / store: every other entry
 // point keeps working on the same environment, and a launch may be split anywhere.
 //
@@ -41,6 +43,8 @@
 // modulations_to_consider == n_mods, n_links <= 32 + kM64HiBits = 41, n_nodes <= 64, every slot count of the traffic table
 // <= min(512, tab_nmax), 2S+1 < 2048, and the policy's LDS block within 160 KiB.
 #pragma once
+#include <type_traits>
+
 #include "ongym_device.hpp"
 
 namespace ongym {
@@ -532,25 +536,36 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
     auto path_and = [&](uint64_t links64) -> uint32_t {
         const int wl = min(lane, RW - 1);
         uint32_t x = lane < RW ? ~0u : 0u;
+        // Two links per trip while two remain: both rows are read before either is used, so a pair costs one LDS round trip
+        // (the same instructions per link; no neutral read pads an odd count).
+        auto row = [](uint32_t a) -> uint32_t { return *(const __attribute__((address_space(3))) uint32_t *)(uintptr_t)a; };
         if (M64) {
             uint64_t links = links64;
             const uint32_t v_word = occ_base + (uint32_t)wl * 4u, v_rw4 = vz + (uint32_t)RW * 4u;
-            while (links) {
+            auto take = [&]() -> uint32_t {
                 const int l = __builtin_ctzll(links);
                 asm("s_bitset0_b64 %0, %1" : "+s"(links) : "s"(l));
-                const uint32_t a = __umul24((uint32_t)l, v_rw4) + v_word;
-                x &= *(const __attribute__((address_space(3))) uint32_t *)(uintptr_t)a;
+                return __umul24((uint32_t)l, v_rw4) + v_word;
+            };
+            while (links) {
+                const uint32_t r0 = row(take());
+                if (links) x &= row(take());
+                x &= r0;
             }
         } else {
             // per link: s_ff1, s_bitset0 (one instruction instead of the add/and pair of links &= links - 1), and the row address
             // lane offset + l * row bytes as one v_mad_u32_u24 on the vector pipe
             uint32_t links = (uint32_t)links64;
             const uint32_t v_word = occ_base + (uint32_t)wl * 4u, v_rw4 = vz + (uint32_t)RW * 4u;
-            while (links) {
+            auto take = [&]() -> uint32_t {
                 const int l = __builtin_ctz(links);
                 asm("s_bitset0_b32 %0, %1" : "+s"(links) : "s"(l));
-                const uint32_t a = __umul24((uint32_t)l, v_rw4) + v_word;
-                x &= *(const __attribute__((address_space(3))) uint32_t *)(uintptr_t)a;
+                return __umul24((uint32_t)l, v_rw4) + v_word;
+            };
+            while (links) {
+                const uint32_t r0 = row(take());
+                if (links) x &= row(take());
+                x &= r0;
             }
         }
         if (lane == (S >> 5)) x |= 1u << (S & 31);
@@ -816,11 +831,8 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
             int e_terms = 0, L = -1, cache_terms = 0;
             double ev_acc = 0.0, ev_ase = 0.0, ev_nli = 0.0;      // results of eval_one for the lane that counts
 
-            // centre, table row, summed link weights (Phi folded in) of running service `idx` as an interferer of the route
-            auto intf_of = [&](int idx, uint32_t mask_lo, uint32_t mask_hi, uint32_t &c2k, uint32_t &key4, double &w1o, double &pw2o) -> int {
-                const uint2 ab = rec[idx];
-                c2k = ab.y & 0x7FFu;
-                key4 = rec_nm1<M64>(ab.y) << 15;                // (n-1) * kTabPitch entries * 16 bytes
+            // weights of the links that record `ab` shares with the route, summed in link order; returns their number
+            auto link_weights = [&](const uint2 ab, uint32_t mask_lo, uint32_t mask_hi, double &w1o, double &w2o) -> int {
                 uint32_t mm = ab.x & mask_lo;
                 double w1 = 0.0, w2 = 0.0;
                 int terms = __popc(mm);
@@ -830,12 +842,33 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                     terms += __popc(mh);
                     while (mh) { const int l = 32 + __ffs(mh) - 1; mh &= mh - 1; w1 += lw[2 * l]; w2 += lw[2 * l + 1]; }
                 }
-                w1o = w1;
+                w1o = w1; w2o = w2;
+                return terms;
+            };
+            // centre, table row, summed link weights (Phi folded in) of running service `idx` as an interferer of the route
+            auto intf_of = [&](int idx, uint32_t mask_lo, uint32_t mask_hi, uint32_t &c2k, uint32_t &key4, double &w1o, double &pw2o) -> int {
+                const uint2 ab = rec[idx];
+                c2k = ab.y & 0x7FFu;
+                key4 = rec_nm1<M64>(ab.y) << 15;                // (n-1) * kTabPitch entries * 16 bytes
+                double w2;
+                const int terms = link_weights(ab, mask_lo, mask_hi, w1o, w2);
                 pw2o = phi[(ab.y >> 11) & 7u] * w2;
                 return terms;
             };
-            // pass 1 of the GN model: interferers of the route -> LDS list -> registers (the first 64*ENT of them)
-            auto build_cache = [&](uint32_t mask_lo, uint32_t mask_hi) {
+            // the pair-table gathers of one evaluation at centre c2 (cache groups without interferers cost nothing)
+            auto gather = [&](uint32_t c2, TabPair (&t)[ENT]) {
+    #pragma unroll
+                for (int e = 0; e < ENT; e++) {
+                    t[e].x = 0.0; t[e].y = 0.0;
+                    if (e == 0 || L > kWave * e) {          // wave-uniform
+                        const uint32_t adi = __builtin_amdgcn_sad_u16(e_c2k[e], c2, 0);
+                        t[e] = load_pair(tab, e_key4[e] | (adi << 4));
+                    }
+                }
+            };
+            // pass 1 of the GN model: interferers of the route -> LDS list -> registers (the first 64*ENT of them).  `t` receives
+            // the gathers of the evaluation at centre c2 that follows the build (not HIGHEST_SNR, which evaluates by candidates).
+            auto build_cache = [&](uint32_t mask_lo, uint32_t mask_hi, uint32_t c2, TabPair (&t)[ENT]) {
                 L = 0;
                 for (int base = 0; base < active; base += 2 * kWave) {
                     const int i0 = base + lane, i1 = i0 + kWave;
@@ -853,12 +886,42 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                 wave_sync();
                 FSTAMP(3);
                 e_terms = 0;
+                // One dependent chain for the NG cache groups that hold interferers: list entries, then records (lanes beyond the
+                // list take the neutral entry: no shared link, zero weights), then Phi and the gathers, which need the record word
+                // alone, and only then the divergent link-weight loops, which run while the gathers are in flight.  The groups
+                // beyond the list read nothing (one wave-uniform branch picks the chain).
+                auto chain = [&](auto ng_) {
+                    constexpr int NG = decltype(ng_)::value;
+                    uint32_t idx[NG];
+                    uint2 ab[NG];
+                    double ph[NG];
     #pragma unroll
-                for (int e = 0; e < ENT; e++) {
-                    const int j = lane + kWave * e;
-                    e_c2k[e] = 0; e_key4[e] = 0; e_w1[e] = 0.0; e_pw2[e] = 0.0;
-                    if (j < L) e_terms += intf_of(list[j], mask_lo, mask_hi, e_c2k[e], e_key4[e], e_w1[e], e_pw2[e]);
-                }
+                    for (int e = 0; e < NG; e++) {
+                        const int j = lane + kWave * e;
+                        idx[e] = (uint32_t)C;
+                        if (j < L) idx[e] = list[j];
+                    }
+    #pragma unroll
+                    for (int e = 0; e < NG; e++) ab[e] = rec[idx[e]];
+    #pragma unroll
+                    for (int e = 0; e < ENT; e++) {
+                        e_c2k[e] = e < NG ? ab[e < NG ? e : 0].y & 0x7FFu : 0u;
+                        e_key4[e] = e < NG ? rec_nm1<M64>(ab[e < NG ? e : 0].y) << 15 : 0u;
+                        e_w1[e] = 0.0; e_pw2[e] = 0.0;
+                    }
+    #pragma unroll
+                    for (int e = 0; e < NG; e++) ph[e] = phi[(ab[e].y >> 11) & 7u];
+                    if (POL != ONGYM_POLICY_HIGHEST_SNR) gather(c2, t);
+    #pragma unroll
+                    for (int e = 0; e < NG; e++) {
+                        double w2;
+                        e_terms += link_weights(ab[e], mask_lo, mask_hi, e_w1[e], w2);
+                        e_pw2[e] = ph[e] * w2;
+                    }
+                };
+                if (L <= kWave) chain(std::integral_constant<int, 1>());
+                else if (ENT <= 2 || L <= 2 * kWave) chain(std::integral_constant<int, 2>());
+                else chain(std::integral_constant<int, ENT>());
                 if (POL == ONGYM_POLICY_HIGHEST_SNR || POL == ONGYM_POLICY_LOWEST_FRAGMENTATION) {
                     int tt = e_terms;       // interferer-link terms of one evaluation on this route (statistics)
                     for (int base = kWave * ENT; base < L; base += kWave)
@@ -875,23 +938,13 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
             // LOAD_BALANCING; `rest` = 0 decides lane q alone), are decided here too, in walk order, and counted as the serial
             // walk counts them: one evaluation each, up to the one that passes.  Returns the lane of the format that passes, or
             // -1 (`rest` then loses the formats decided); ev_acc (and ev_ase / ev_nli when records are written) hold its values.
+            // `t`: the cached interferers' table values at this centre (gather(), or build_cache() for the evaluation after a build).
             auto eval_one = [&](int first, int nn, int q, uint32_t &rest, const PathRec &pr, double l_a, double l_b, double l_d,
-                                double l_nlic, double l_lo, double l_hi) -> int {
+                                double l_nlic, double l_lo, double l_hi, const TabPair (&t)[ENT]) -> int {
                 const uint32_t c2 = (uint32_t)(2 * first + nn);
                 double part = 0.0;
-                {
-                    TabPair t[ENT];
-    #pragma unroll
-                    for (int e = 0; e < ENT; e++) {
-                        t[e].x = 0.0; t[e].y = 0.0;
-                        if (e == 0 || L > kWave * e) {          // wave-uniform: a cache group without interferers costs nothing
-                            const uint32_t adi = __builtin_amdgcn_sad_u16(e_c2k[e], c2, 0);
-                            t[e] = load_pair(tab, e_key4[e] | (adi << 4));
-                        }
-                    }
     #pragma unroll              // (a group without interferers has zero weights and zero table values: no select needed)
-                    for (int e = 0; e < ENT; e++) part = fma(t[e].x, e_w1[e], fma(-t[e].y, e_pw2[e], part));
-                }
+                for (int e = 0; e < ENT; e++) part = fma(t[e].x, e_w1[e], fma(-t[e].y, e_pw2[e], part));
                 int x_terms = 0;        // interferer-link terms beyond the register cache
                 for (int base = kWave * ENT; base < L; base += kWave) {       // interferers beyond the register cache
                     const int j = base + lane;
@@ -1087,7 +1140,10 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                 const int first_w = __builtin_ctzll(has);
                 const int first = first_w * 32 + __builtin_ctz(rl(runs, first_w));       // == first_set32(runs)
                 if (POL == ONGYM_POLICY_HIGHEST_SNR && !((__ballot(lb < best_acc) >> q) & 1ull)) continue;   // best_acc may have improved
-                if (L < 0) build_cache(pr.mask_lo, pr.mask_hi);
+                // the first start and the width are known: the build issues this evaluation's gathers before it sums the link weights
+                TabPair tv[ENT];
+                if (L < 0) build_cache(pr.mask_lo, pr.mask_hi, (uint32_t)(2 * first + nn), tv);
+                else if (POL != ONGYM_POLICY_HIGHEST_SNR) gather((uint32_t)(2 * first + nn), tv);
                 FSTAMP(4);
                 if (POL == ONGYM_POLICY_HIGHEST_SNR) {
                     const int cnt = compact_starts(runs);
@@ -1098,7 +1154,7 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                 }
                 uint32_t none = 0;
                 const int ln = eval_one(first, nn, q, POL == ONGYM_POLICY_LOWEST_FRAGMENTATION ? none : feas, pr, r_a, r_b, r_d, w_nlic,
-                                        w_lim_lo, w_lim_hi);
+                                        w_lim_lo, w_lim_hi, tv);
                 FSTAMP(5);
                 if (ln >= 0) {          // all formats of the group have n slots
                     ch_k = k; ch_m = ln & 7; ch_slot = first; ch_n = n; ch_path = path;
@@ -1122,8 +1178,10 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                 // request and flags it (as k_run does).  Same route: the interferer cache is the one just used.
                 const LaneFac sf = lane_fac(t_n, t_nlic, t_selfa);
                 uint32_t none = 0;
+                TabPair tv[ENT];
+                gather((uint32_t)(2 * ch_slot + ch_n), tv);
                 if (eval_one(ch_slot, ch_n, 8 * cur_bi + ch_m, none, pr, sf.c1 * pr.ase, sf.cb * pr.ase, sf.c2 * pr.w1, t_nlic, t_lim_lo,
-                             t_lim_hi) >= 0) {
+                             t_lim_hi, tv) >= 0) {
                     ch_acc = ev_acc; ch_ase = ev_ase; ch_nli = ev_nli;
                 } else { ch_k = -1; lf_qot = true; }
                 break;
@@ -1279,7 +1337,13 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                 const int ln = 63 - __builtin_clzll(bal);                   // highest index first: the hole is filled by a keeper
                 asm("s_bitset0_b64 %0, %1" : "+s"(bal) : "s"(ln));
                 const int idx = ch * kWave + ln;
-                const uint2 ab = rec[idx + vz];                             // same address in every lane: broadcast read
+                uint2 ab = rec[idx + vz];                                   // same address in every lane: broadcast read
+                // the last record, which fills the hole below, is read in the same round trip (freeing slots does not touch it)
+                const int last = active - 1;
+                const uint32_t v_last = vz + (uint32_t)last;
+                const uint2 lab = rec[v_last];
+                const float lr = rr[v_last];
+                asm volatile("" : "+v"(ab.x), "+v"(ab.y));                  // both words now: word y is not fetched again behind the link test
                 const uint32_t nk = rec_nm1<M64>(ab.y) + 1u, sk = ((ab.y & 0x7FFu) - nk) >> 1;
                 const uint32_t hi = min(sk + nk + 1u, (uint32_t)S);         // frees n+1 slots, clamped at S (quirk Q7)
                 if (!WIDE || __builtin_amdgcn_readfirstlane(nk) <= 32u)
@@ -1292,12 +1356,8 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                 }
                 if (POL == ONGYM_POLICY_LOWEST_FRAGMENTATION)          // the departed service's links: their rows changed
                     ls_dirty |= lane < 32 ? ((ab.x >> lane) & 1u) != 0 : (M64 && (((ab.y >> 23) >> (lane - 32)) & 1u) != 0);
-                const int last = active - 1;
                 // lane 0 moves the last record into the hole, lane 1 neutralises the vacated entry (both write the neutral entry when the
                 // hole IS the last record): one masked pair of writes, addresses and data formed on the vector pipe
-                const uint32_t v_last = vz + (uint32_t)last;
-                const uint2 lab = rec[v_last];
-                const float lr = rr[v_last];
                 const bool mv = lane == 0 && idx != last;
                 const uint32_t e = lane == 0 ? (uint32_t)idx + vz : v_last;
                 lds_write_lanes01(rec_base + e * 8u, mv ? lab.x : 0u, mv ? lab.y : 0u, rr_base + e * 4u, mv ? __float_as_uint(lr) : 0x7F800000u);

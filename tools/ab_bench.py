@@ -38,8 +38,10 @@ ap.add_argument("--steps", type=int, default=250)
 ap.add_argument("--warm", type=int, default=1000)
 ap.add_argument("--workload", default="nsfnet320")
 ap.add_argument("--capacity", type=int, default=0)
+ap.add_argument("--per-round", action="store_true", help="also print every round's median (the spread of a build against itself)")
 a = ap.parse_args()
 res = {l: [] for l in a.libs}
+rounds = {l: [] for l in a.libs}
 check = {}
 for rd in range(a.rounds):
     for lib in a.libs:
@@ -50,6 +52,7 @@ for rd in range(a.rounds):
             print(lib, "FAILED", out.stderr[-800:]); continue
         r = json.loads(out.stdout.strip().splitlines()[-1])
         res[lib] += r["ms"]; check[lib] = (r["acc"], r["steps"])
+        rounds[lib].append(sorted(r["ms"])[len(r["ms"]) // 2])
 for lib in a.libs:
     ms = sorted(res[lib])
     if not ms:
@@ -57,3 +60,5 @@ for lib in a.libs:
     med = ms[len(ms) // 2]
     mean = sum(ms) / len(ms)
     print(f"{os.path.basename(lib):40s} min {ms[0]:8.2f} ms  med {med:8.2f} ms  mean {mean:8.3f} ms -> {a.batch * a.steps / mean * 1e3:.4e} steps/s   accepted/steps {check[lib]}")
+    if a.per_round:
+        print(f"{'':40s} round medians " + " ".join(f"{m:.3f}" for m in rounds[lib]) + f"  spread {max(rounds[lib]) - min(rounds[lib]):.3f} ms")
