@@ -185,13 +185,7 @@ __global__ __launch_bounds__(64) void k_observe_blocks(const Params *__restrict_
     extern __shared__ __align__(16) unsigned char smem[];
     const Params &P = *Pp;
     Ctx c(P);
-    c.lane = threadIdx.x;
-    c.replica = blockIdx.x;
-    c.lane_terms = 0;
-    c.gn_evals = 0;
-    c.gn_skips = 0;
-    c.paths_tried = 0; c.path_hops = 0; c.active_sum = 0;
-    ctx_bind(c, smem);
+    ctx_open(c, smem, blockIdx.x);
     load_state(c);
     unsigned char *x = smem + blocks_lds_offset(P);
     uint64_t *row = reinterpret_cast<uint64_t *>(x);

@@ -269,6 +269,17 @@ __device__ __forceinline__ void ctx_bind(Ctx &c, unsigned char *smem) {
     c.sq = reinterpret_cast<uint32_t *>(c.so + P.capacity);
 }
 
+// How every one-wavefront-per-replica kernel starts: this lane, its replica, the launch's counters at zero, the LDS carve-up
+__device__ __forceinline__ void ctx_open(Ctx &c, unsigned char *smem, int replica) {
+    c.lane = threadIdx.x;
+    c.replica = replica;
+    c.lane_terms = 0;
+    c.gn_evals = 0;
+    c.gn_skips = 0;
+    c.paths_tried = 0; c.path_hops = 0; c.active_sum = 0;
+    ctx_bind(c, smem);
+}
+
 // Table pointers live in a Params object read from memory, so the compiler cannot know they are global and would emit
 // flat_load (which also ties up the LDS counter). G() states the address space.
 template <class T>

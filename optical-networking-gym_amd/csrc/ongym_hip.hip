@@ -42,13 +42,7 @@ __global__ __launch_bounds__(64, WAVES) void k_run(const Params *__restrict__ Pp
     extern __shared__ __align__(16) unsigned char smem[];
     const Params &P = *Pp;
     Ctx c(P);
-    c.lane = threadIdx.x;
-    c.replica = blockIdx.x;
-    c.lane_terms = 0;
-    c.gn_evals = 0;
-    c.gn_skips = 0;
-    c.paths_tried = 0; c.path_hops = 0; c.active_sum = 0;
-    ctx_bind(c, smem);
+    ctx_open(c, smem, blockIdx.x);
 #ifdef ONGYM_STAMPS
     for (int i = 0; i < ONGYM_NSTAMPS; i++) c.stamp_acc[i] = 0;
     c.stamp_last = __builtin_amdgcn_s_memtime();
@@ -131,13 +125,7 @@ __global__ __launch_bounds__(64) void k_reset(const Params *__restrict__ Pp, con
     if (mask && !mask[blockIdx.x]) return;
     const Params &P = *Pp;
     Ctx c(P);
-    c.lane = threadIdx.x;
-    c.replica = blockIdx.x;
-    c.lane_terms = 0;
-    c.gn_evals = 0;
-    c.gn_skips = 0;
-    c.paths_tried = 0; c.path_hops = 0; c.active_sum = 0;
-    ctx_bind(c, smem);
+    ctx_open(c, smem, blockIdx.x);
     load_state(c);
     reset_env(c);
     store_state(c);
@@ -151,13 +139,7 @@ __global__ __launch_bounds__(64, ONGYM_OBS_WAVES) void k_observe(const Params *_
     extern __shared__ __align__(16) unsigned char smem[];
     const Params &P = *Pp;
     Ctx c(P);
-    c.lane = threadIdx.x;
-    c.replica = blockIdx.x;
-    c.lane_terms = 0;
-    c.gn_evals = 0;
-    c.gn_skips = 0;
-    c.paths_tried = 0; c.path_hops = 0; c.active_sum = 0;
-    ctx_bind(c, smem);
+    ctx_open(c, smem, blockIdx.x);
 #ifdef ONGYM_STAMPS
     for (int i = 0; i < ONGYM_NSTAMPS; i++) c.stamp_acc[i] = 0;
     c.stamp_last = __builtin_amdgcn_s_memtime();
@@ -272,13 +254,7 @@ __global__ __launch_bounds__(64) void k_query_gsnr_many(const Params *__restrict
     const Params &P = *Pp;
     if ((int)blockIdx.x >= count) return;
     Ctx c(P);
-    c.lane = threadIdx.x;
-    c.replica = replica;
-    c.lane_terms = 0;
-    c.gn_evals = 0;
-    c.gn_skips = 0;
-    c.paths_tried = 0; c.path_hops = 0; c.active_sum = 0;
-    ctx_bind(c, smem);
+    ctx_open(c, smem, replica);
     load_state(c);
     const int path = cand[3 * blockIdx.x], slot = cand[3 * blockIdx.x + 1], n = cand[3 * blockIdx.x + 2];
     PathRef p = load_path(c, path);
@@ -297,13 +273,7 @@ __global__ __launch_bounds__(64) void k_query(const Params *__restrict__ Pp, int
     extern __shared__ __align__(16) unsigned char smem[];
     const Params &P = *Pp;
     Ctx c(P);
-    c.lane = threadIdx.x;
-    c.replica = replica;
-    c.lane_terms = 0;
-    c.gn_evals = 0;
-    c.gn_skips = 0;
-    c.paths_tried = 0; c.path_hops = 0; c.active_sum = 0;
-    ctx_bind(c, smem);
+    ctx_open(c, smem, replica);
     load_state(c);
     if (what == kQAvailable) {          // get_available_slots(path), envs/qrmsa.pyx:1482-1512
         PathRef p = load_path(c, path);
@@ -500,6 +470,78 @@ static int dev_alloc(ongym_env *env, size_t n, T **dst, bool zero) {
 static int fail_arg(ongym_env *env, const char *msg, int code = ONGYM_E_ARG) {
     env->err = msg;
     return code;
+}
+
+static int need_source(ongym_env *env) {
+    return fail_arg(env, "no request source: call ongym_seed or ongym_set_requests first", ONGYM_E_STATE);
+}
+
+// f() launches kernels on the environment's stream: ongym_last_kernel_ms reports the time between the two events
+template <class F>
+static int timed_launch(ongym_env *env, F &&f) {
+    HIP_TRY(env, hipEventRecord(env->ev0, env->stream));
+    if (const int rc = f()) return rc;
+    HIP_TRY(env, hipEventRecord(env->ev1, env->stream));
+    env->timed = true;
+    return 0;
+}
+
+// One array of an analysis call: the caller's pointer (null: an optional array that is not asked for), its size, whether the
+// kernel reads it (kIn), writes it (kOut) or both, and, after stage_open, the pointer the kernel gets.
+enum { kIn = 1, kOut = 2 };
+struct Span {
+    const void *host; size_t bytes; int dir;
+    void *dev;
+    template <class T> T *as() const { return static_cast<T *>(dev); }
+};
+
+// Device pointers for the arrays of a call, given in layout order.  With io_device they are the caller's.  Otherwise the arrays
+// lie in `st` at 256-byte offsets (an array that is not asked for takes no room and gets a null pointer, which the kernels
+// branch on), `st` is grown if it is too small, and the kIn arrays are copied in.
+template <size_t N>
+static int stage_open(ongym_env *env, Stage &st, Span (&sp)[N]) {
+    if (env->cfg.io_device) {
+        for (Span &s : sp) s.dev = const_cast<void *>(s.host);
+        return 0;
+    }
+    size_t off[N], total = 0;
+    for (size_t i = 0; i < N; i++) {
+        if (!sp[i].host) sp[i].bytes = 0;
+        off[i] = (total + 255) & ~(size_t)255;
+        total = off[i] + sp[i].bytes;
+    }
+    if (st.bytes < total) {
+        if (st.base) { (void)hipFree(st.base); st.base = nullptr; st.bytes = 0; }
+        HIP_TRY(env, hipMalloc(&st.base, total));
+        st.bytes = total;
+    }
+    for (size_t i = 0; i < N; i++) {
+        Span &s = sp[i];
+        s.dev = s.host ? static_cast<char *>(st.base) + off[i] : nullptr;
+        if (s.host && (s.dir & kIn)) HIP_TRY(env, hipMemcpyAsync(s.dev, s.host, s.bytes, hipMemcpyHostToDevice, env->stream));
+    }
+    return 0;
+}
+
+// After the launch: the kOut arrays back to the caller and one synchronisation (nothing with io_device)
+template <size_t N>
+static int stage_close(ongym_env *env, const Span (&sp)[N]) {
+    if (env->cfg.io_device) return ONGYM_OK;
+    for (const Span &s : sp)
+        if (s.host && (s.dir & kOut))
+            HIP_TRY(env, hipMemcpyAsync(const_cast<void *>(s.host), s.dev, s.bytes, hipMemcpyDeviceToHost, env->stream));
+    HIP_TRY(env, hipStreamSynchronize(env->stream));
+    return ONGYM_OK;
+}
+
+// The optional reset mask [batch] as the kernels read it: the caller's pointer with io_device, else a device copy
+static int stage_reset_mask(ongym_env *env, const uint8_t *mask, const uint8_t **dmask) {
+    *dmask = mask;
+    if (mask && !env->cfg.io_device) {
+        HIP_TRY(env, hipMemcpyAsync(env->d_mask, mask, (size_t)env->P.batch, hipMemcpyHostToDevice, env->stream));
+        *dmask = env->d_mask;
+    }
+    return 0;
 }
 
 static int build(ongym_env *env, const ongym_config *c) {
@@ -1073,10 +1115,7 @@ void ongym_destroy(ongym_env *env) {
     if (env->d_out) (void)hipFree(env->d_out);
     if (env->h_pinned) (void)hipHostFree(env->h_pinned);
     if (env->d_state_stage) (void)hipFree(env->d_state_stage);
-    if (env->d_blocks) (void)hipFree(env->d_blocks);
-    if (env->d_metrics) (void)hipFree(env->d_metrics);
-    if (env->d_qot) (void)hipFree(env->d_qot);
-    if (env->d_impact) (void)hipFree(env->d_impact);
+    for (Stage &st : env->stage) if (st.base) (void)hipFree(st.base);
     if (env->ev0) (void)hipEventDestroy(env->ev0);
     if (env->ev1) (void)hipEventDestroy(env->ev1);
     if (env->own_stream) (void)hipStreamDestroy(env->own_stream);      // a caller's stream (ongym_set_stream) is the caller's
@@ -1193,16 +1232,10 @@ int ongym_set_requests(ongym_env *env, const ongym_request *reqs, int64_t n_per_
 
 int ongym_reset(ongym_env *env, const uint8_t *mask) {
     if (!env) return ONGYM_E_ARG;
-    if (!env->has_source) { env->err = "no request source: call ongym_seed or ongym_set_requests first"; return ONGYM_E_STATE; }
+    if (!env->has_source) return need_source(env);
     HIP_TRY(env, hipSetDevice(env->cfg.device));
-    const uint8_t *dmask = nullptr;
-    if (mask) {
-        if (env->cfg.io_device) dmask = mask;
-        else {
-            HIP_TRY(env, hipMemcpyAsync(env->d_mask, mask, (size_t)env->P.batch, hipMemcpyHostToDevice, env->stream));
-            dmask = env->d_mask;
-        }
-    }
+    const uint8_t *dmask;
+    if (int rc = stage_reset_mask(env, mask, &dmask)) return rc;
     return launch_lds(env, k_reset, dim3(env->P.batch), env->lds, env->d_P, dmask);
 }
 
@@ -1214,14 +1247,8 @@ int ongym_reset_episode_counters(ongym_env *env, const uint8_t *mask) {
         return ONGYM_E_STATE;
     }
     HIP_TRY(env, hipSetDevice(env->cfg.device));
-    const uint8_t *dmask = nullptr;
-    if (mask) {
-        if (env->cfg.io_device) dmask = mask;
-        else {
-            HIP_TRY(env, hipMemcpyAsync(env->d_mask, mask, (size_t)env->P.batch, hipMemcpyHostToDevice, env->stream));
-            dmask = env->d_mask;
-        }
-    }
+    const uint8_t *dmask;
+    if (int rc = stage_reset_mask(env, mask, &dmask)) return rc;
     int threads = 64, blocks = (env->P.batch + threads - 1) / threads;
     hipLaunchKernelGGL(k_reset_counters, dim3(blocks), dim3(threads), 0, env->stream, env->P, dmask);
     HIP_TRY(env, hipGetLastError());
@@ -1230,17 +1257,14 @@ int ongym_reset_episode_counters(ongym_env *env, const uint8_t *mask) {
 
 static int launch_run(ongym_env *env, int mode, int policy, int nsteps, const int32_t *d_actions, int32_t *d_act_out,
                       uint8_t *d_flag_out, ongym_step_rec *d_out) {
-    HIP_TRY(env, hipEventRecord(env->ev0, env->stream));
     // the lean kernels: same results, half the issued instructions (ongym_fast.hpp)
     const LeanFns *lean = mode == kModePolicyStep ? lean_unit(env, policy) : nullptr;
-    const int rc = lean ? lean->launch(env, nsteps, d_out) : with_run_kernel(env, policy, [&](auto kernel, size_t lds) {
-        return launch_lds(env, kernel, dim3(env->P.batch), lds, env->d_P, mode, nsteps, d_actions, d_act_out, d_flag_out, d_out,
-                          policy);
+    return timed_launch(env, [&] {
+        return lean ? lean->launch(env, nsteps, d_out) : with_run_kernel(env, policy, [&](auto kernel, size_t lds) {
+            return launch_lds(env, kernel, dim3(env->P.batch), lds, env->d_P, mode, nsteps, d_actions, d_act_out, d_flag_out,
+                              d_out, policy);
+        });
     });
-    if (rc) return rc;
-    HIP_TRY(env, hipEventRecord(env->ev1, env->stream));
-    env->timed = true;
-    return 0;
 }
 
 static int ensure_out(ongym_env *env, size_t n) {
@@ -1267,7 +1291,7 @@ int ongym_step_policy(ongym_env *env, int32_t policy, int32_t nsteps, ongym_step
     int rc;
     if ((rc = check_policy(env, policy))) return rc;
     if (nsteps <= 0) return fail_arg(env, "nsteps must be positive");
-    if (!env->has_source) { env->err = "no request source: call ongym_seed or ongym_set_requests first"; return ONGYM_E_STATE; }
+    if (!env->has_source) return need_source(env);
     HIP_TRY(env, hipSetDevice(env->cfg.device));
     if (out && !env->cfg.io_device) {
         size_t n = (size_t)nsteps * env->P.batch;
@@ -1282,7 +1306,7 @@ int ongym_step_policy(ongym_env *env, int32_t policy, int32_t nsteps, ongym_step
 
 int ongym_step_actions(ongym_env *env, const int32_t *actions, ongym_step_rec *out) {
     if (!env || !actions) return env ? fail_arg(env, "null actions") : ONGYM_E_ARG;
-    if (!env->has_source) { env->err = "no request source: call ongym_seed or ongym_set_requests first"; return ONGYM_E_STATE; }
+    if (!env->has_source) return need_source(env);
     HIP_TRY(env, hipSetDevice(env->cfg.device));
     int rc;
     if (env->cfg.io_device) return launch_run(env, kModeActionStep, ONGYM_POLICY_FIRST_FIT, 1, actions, nullptr, nullptr, out);
@@ -1301,7 +1325,7 @@ int ongym_step_actions_bundle(ongym_env *env, const int32_t *actions, int32_t ne
     if (!env || !actions || !rec_out || !request_out || !stats_out) return env ? fail_arg(env, "null buffer") : ONGYM_E_ARG;
     if (env->cfg.io_device) return fail_arg(env, "ongym_step_actions_bundle returns host buffers: not with io_device", ONGYM_E_STATE);
     if (next_policy >= 0 && (!next_actions || !next_flags)) return fail_arg(env, "null next_actions / next_flags");
-    if (!env->has_source) { env->err = "no request source: call ongym_seed or ongym_set_requests first"; return ONGYM_E_STATE; }
+    if (!env->has_source) return need_source(env);
     int rc;
     if (next_policy >= 0 && (rc = check_policy(env, next_policy))) return rc;
     HIP_TRY(env, hipSetDevice(env->cfg.device));
@@ -1376,13 +1400,12 @@ int ongym_observe(ongym_env *env, float *obs, uint8_t *mask) {
         d_obs = env->d_obs; d_mask = env->d_obsmask;
     }
     HIP_TRY(env, hipMemsetAsync(d_mask, 0, B * nact, env->stream));     // k_observe only sets the ones
-    HIP_TRY(env, hipEventRecord(env->ev0, env->stream));
-    const int rc = with_layout(P, [&](auto UA, auto R32) {
-        return launch_lds(env, k_observe<UA, R32>, dim3(P.batch), obs_layout(P).total, env->d_P, d_obs, d_mask);
+    const int rc = timed_launch(env, [&] {
+        return with_layout(P, [&](auto UA, auto R32) {
+            return launch_lds(env, k_observe<UA, R32>, dim3(P.batch), obs_layout(P).total, env->d_P, d_obs, d_mask);
+        });
     });
     if (rc) return rc;
-    HIP_TRY(env, hipEventRecord(env->ev1, env->stream));
-    env->timed = true;
     if (!env->cfg.io_device) {
         HIP_TRY(env, hipMemcpyAsync(obs, d_obs, B * obs_dim * sizeof(float), hipMemcpyDeviceToHost, env->stream));
         HIP_TRY(env, hipMemcpyAsync(mask, d_mask, B * nact, hipMemcpyDeviceToHost, env->stream));
@@ -1400,33 +1423,18 @@ int ongym_observe_blocks(ongym_env *env, int32_t blocks, float *obs, uint8_t *ma
         return fail_arg(env, "the block action space has no format window: it needs modulations_to_consider == n_mods");
     if (!P.path_len_norm || !(P.max_bit_rate > 0)) return fail_arg(env, "block observation needs path_len_norm and max_bit_rate = max(bit_rates)");
     HIP_TRY(env, hipSetDevice(env->cfg.device));
-    const size_t B = (size_t)P.batch, J = (size_t)blocks, nout = (size_t)P.k_paths * J + 1;
-    const size_t obs_b = B * (size_t)blocks_obs_dim(P.k_paths, blocks) * sizeof(float), map_b = B * nout * sizeof(int32_t), mask_b = B * nout;
-    float *d_obs = obs; uint8_t *d_mask = mask; int32_t *d_map = action_map;
-    if (!env->cfg.io_device) {       // staging: obs | action_map | mask, grown on demand
-        const size_t o_map = (obs_b + 255) & ~(size_t)255, o_mask = (o_map + map_b + 255) & ~(size_t)255, total = o_mask + mask_b;
-        if (env->d_blocks_bytes < total) {
-            if (env->d_blocks) { (void)hipFree(env->d_blocks); env->d_blocks = nullptr; env->d_blocks_bytes = 0; }
-            HIP_TRY(env, hipMalloc(&env->d_blocks, total));
-            env->d_blocks_bytes = total;
-        }
-        char *base = static_cast<char *>(env->d_blocks);
-        d_obs = reinterpret_cast<float *>(base); d_map = reinterpret_cast<int32_t *>(base + o_map); d_mask = reinterpret_cast<uint8_t *>(base + o_mask);
-    }
-    HIP_TRY(env, hipEventRecord(env->ev0, env->stream));
-    const int rc = with_layout(P, [&](auto UA, auto R32) {   // the step kernels' (UA, R32): the same QoT decisions
-        return launch_lds(env, k_observe_blocks<UA, R32>, dim3(P.batch), blocks_lds_bytes(P), env->d_P, (int)blocks, d_obs, d_mask, d_map);
+    const size_t B = (size_t)P.batch, nout = (size_t)P.k_paths * blocks + 1;
+    Span sp[] = {{obs, B * (size_t)blocks_obs_dim(P.k_paths, blocks) * sizeof(float), kOut},       // staging: obs | action_map | mask
+                 {action_map, B * nout * sizeof(int32_t), kOut}, {mask, B * nout, kOut}};
+    int rc;
+    if ((rc = stage_open(env, env->stage[kStageBlocks], sp))) return rc;
+    rc = timed_launch(env, [&] {
+        return with_layout(P, [&](auto UA, auto R32) {   // the step kernels' (UA, R32): the same QoT decisions
+            return launch_lds(env, k_observe_blocks<UA, R32>, dim3(P.batch), blocks_lds_bytes(P), env->d_P, (int)blocks,
+                              sp[0].as<float>(), sp[2].as<uint8_t>(), sp[1].as<int32_t>());
+        });
     });
-    if (rc) return rc;
-    HIP_TRY(env, hipEventRecord(env->ev1, env->stream));
-    env->timed = true;
-    if (!env->cfg.io_device) {
-        HIP_TRY(env, hipMemcpyAsync(obs, d_obs, obs_b, hipMemcpyDeviceToHost, env->stream));
-        HIP_TRY(env, hipMemcpyAsync(mask, d_mask, mask_b, hipMemcpyDeviceToHost, env->stream));
-        HIP_TRY(env, hipMemcpyAsync(action_map, d_map, map_b, hipMemcpyDeviceToHost, env->stream));
-        HIP_TRY(env, hipStreamSynchronize(env->stream));
-    }
-    return ONGYM_OK;
+    return rc ? rc : stage_close(env, sp);
 }
 
 int ongym_link_metrics(ongym_env *env, float *link_out, double *compactness, double *link_stats) {
@@ -1435,36 +1443,17 @@ int ongym_link_metrics(ongym_env *env, float *link_out, double *compactness, dou
     const Params &P = env->P;
     HIP_TRY(env, hipSetDevice(env->cfg.device));
     const size_t B = (size_t)P.batch, E = (size_t)P.n_links;
-    const size_t out_b = link_out ? B * E * kLinkMetrics * sizeof(float) : 0, comp_b = compactness ? B * sizeof(double) : 0;
-    const size_t stats_b = link_stats ? B * E * kLinkStats * sizeof(double) : 0;
-    float *d_out = link_out; double *d_comp = compactness, *d_stats = link_stats;
-    if (!env->cfg.io_device) {       // staging: link_stats | compactness | link_out, grown on demand
-        const size_t o_comp = (stats_b + 255) & ~(size_t)255, o_out = (o_comp + comp_b + 255) & ~(size_t)255, total = o_out + out_b;
-        if (env->d_metrics_bytes < total) {
-            if (env->d_metrics) { (void)hipFree(env->d_metrics); env->d_metrics = nullptr; env->d_metrics_bytes = 0; }
-            HIP_TRY(env, hipMalloc(&env->d_metrics, total));
-            env->d_metrics_bytes = total;
-        }
-        char *base = static_cast<char *>(env->d_metrics);
-        d_stats = link_stats ? reinterpret_cast<double *>(base) : nullptr;
-        d_comp = compactness ? reinterpret_cast<double *>(base + o_comp) : nullptr;
-        d_out = link_out ? reinterpret_cast<float *>(base + o_out) : nullptr;
-        if (link_stats) HIP_TRY(env, hipMemcpyAsync(d_stats, link_stats, stats_b, hipMemcpyHostToDevice, env->stream));
-    }
-    HIP_TRY(env, hipEventRecord(env->ev0, env->stream));
-    const int rc = with_layout(P, [&](auto, auto R32) {     // the stored record codec
-        return launch_lds(env, k_link_metrics<R32>, dim3(P.batch), metrics_lds_bytes(P), env->d_P, d_out, d_comp, d_stats);
+    Span sp[] = {{link_stats, B * E * kLinkStats * sizeof(double), kIn | kOut},                    // staging: link_stats | compactness | link_out
+                 {compactness, B * sizeof(double), kOut}, {link_out, B * E * kLinkMetrics * sizeof(float), kOut}};
+    int rc;
+    if ((rc = stage_open(env, env->stage[kStageMetrics], sp))) return rc;
+    rc = timed_launch(env, [&] {
+        return with_layout(P, [&](auto, auto R32) {     // the stored record codec
+            return launch_lds(env, k_link_metrics<R32>, dim3(P.batch), metrics_lds_bytes(P), env->d_P, sp[2].as<float>(),
+                              sp[1].as<double>(), sp[0].as<double>());
+        });
     });
-    if (rc) return rc;
-    HIP_TRY(env, hipEventRecord(env->ev1, env->stream));
-    env->timed = true;
-    if (!env->cfg.io_device) {
-        if (link_out) HIP_TRY(env, hipMemcpyAsync(link_out, d_out, out_b, hipMemcpyDeviceToHost, env->stream));
-        if (compactness) HIP_TRY(env, hipMemcpyAsync(compactness, d_comp, comp_b, hipMemcpyDeviceToHost, env->stream));
-        if (link_stats) HIP_TRY(env, hipMemcpyAsync(link_stats, d_stats, stats_b, hipMemcpyDeviceToHost, env->stream));
-        HIP_TRY(env, hipStreamSynchronize(env->stream));
-    }
-    return ONGYM_OK;
+    return rc ? rc : stage_close(env, sp);
 }
 
 int ongym_service_qot(ongym_env *env, double *svc_out, double *replica_out, float *link_out) {
@@ -1475,36 +1464,17 @@ int ongym_service_qot(ongym_env *env, double *svc_out, double *replica_out, floa
     if (lds > 160 * 1024) return fail_arg(env, "the QoT kernel's LDS block exceeds 160 KiB: lower capacity", ONGYM_E_LIMIT);
     HIP_TRY(env, hipSetDevice(env->cfg.device));
     const size_t B = (size_t)P.batch;
-    const size_t svc_b = svc_out ? B * P.capacity * kServiceQot * sizeof(double) : 0;
-    const size_t rep_b = replica_out ? B * kReplicaQot * sizeof(double) : 0;
-    const size_t link_b = link_out ? B * P.n_links * kLinkQot * sizeof(float) : 0;
-    double *d_svc = svc_out, *d_rep = replica_out; float *d_link = link_out;
-    if (!env->cfg.io_device) {       // staging: svc_out | replica_out | link_out, grown on demand
-        const size_t o_rep = (svc_b + 255) & ~(size_t)255, o_link = (o_rep + rep_b + 255) & ~(size_t)255, total = o_link + link_b;
-        if (env->d_qot_bytes < total) {
-            if (env->d_qot) { (void)hipFree(env->d_qot); env->d_qot = nullptr; env->d_qot_bytes = 0; }
-            HIP_TRY(env, hipMalloc(&env->d_qot, total));
-            env->d_qot_bytes = total;
-        }
-        char *base = static_cast<char *>(env->d_qot);
-        d_svc = svc_out ? reinterpret_cast<double *>(base) : nullptr;
-        d_rep = replica_out ? reinterpret_cast<double *>(base + o_rep) : nullptr;
-        d_link = link_out ? reinterpret_cast<float *>(base + o_link) : nullptr;
-    }
-    HIP_TRY(env, hipEventRecord(env->ev0, env->stream));
-    const int rc = with_layout(P, [&](auto UA, auto R32) {     // attenuation and the stored record codec
-        return launch_lds(env, k_service_qot<UA, R32>, dim3(P.batch), lds, env->d_P, d_svc, d_rep, d_link);
+    Span sp[] = {{svc_out, B * P.capacity * kServiceQot * sizeof(double), kOut},                   // staging: svc_out | replica_out | link_out
+                 {replica_out, B * kReplicaQot * sizeof(double), kOut}, {link_out, B * P.n_links * kLinkQot * sizeof(float), kOut}};
+    int rc;
+    if ((rc = stage_open(env, env->stage[kStageQot], sp))) return rc;
+    rc = timed_launch(env, [&] {
+        return with_layout(P, [&](auto UA, auto R32) {     // attenuation and the stored record codec
+            return launch_lds(env, k_service_qot<UA, R32>, dim3(P.batch), lds, env->d_P, sp[0].as<double>(), sp[1].as<double>(),
+                              sp[2].as<float>());
+        });
     });
-    if (rc) return rc;
-    HIP_TRY(env, hipEventRecord(env->ev1, env->stream));
-    env->timed = true;
-    if (!env->cfg.io_device) {
-        if (svc_out) HIP_TRY(env, hipMemcpyAsync(svc_out, d_svc, svc_b, hipMemcpyDeviceToHost, env->stream));
-        if (replica_out) HIP_TRY(env, hipMemcpyAsync(replica_out, d_rep, rep_b, hipMemcpyDeviceToHost, env->stream));
-        if (link_out) HIP_TRY(env, hipMemcpyAsync(link_out, d_link, link_b, hipMemcpyDeviceToHost, env->stream));
-        HIP_TRY(env, hipStreamSynchronize(env->stream));
-    }
-    return ONGYM_OK;
+    return rc ? rc : stage_close(env, sp);
 }
 
 int ongym_action_impact(ongym_env *env, int32_t n_actions, const int32_t *actions, const double *svc_in, double *impact_out) {
@@ -1516,37 +1486,17 @@ int ongym_action_impact(ongym_env *env, int32_t n_actions, const int32_t *action
     if (lds > 160 * 1024) return fail_arg(env, "the impact kernel's LDS block exceeds 160 KiB: lower capacity", ONGYM_E_LIMIT);
     HIP_TRY(env, hipSetDevice(env->cfg.device));
     const size_t B = (size_t)P.batch, A = (size_t)n_actions;
-    const size_t act_b = B * A * sizeof(int32_t), out_b = B * A * kActionImpact * sizeof(double);
-    const size_t svc_b = svc_in ? B * P.capacity * kServiceQot * sizeof(double) : 0;
-    const int32_t *d_act = actions; const double *d_svc = svc_in; double *d_out = impact_out;
-    if (!env->cfg.io_device) {       // staging: impact_out | svc_in | actions, grown on demand
-        const size_t o_svc = (out_b + 255) & ~(size_t)255, o_act = (o_svc + svc_b + 255) & ~(size_t)255, total = o_act + act_b;
-        if (env->d_impact_bytes < total) {
-            if (env->d_impact) { (void)hipFree(env->d_impact); env->d_impact = nullptr; env->d_impact_bytes = 0; }
-            HIP_TRY(env, hipMalloc(&env->d_impact, total));
-            env->d_impact_bytes = total;
-        }
-        char *base = static_cast<char *>(env->d_impact);
-        d_out = reinterpret_cast<double *>(base);
-        HIP_TRY(env, hipMemcpyAsync(base + o_act, actions, act_b, hipMemcpyHostToDevice, env->stream));
-        d_act = reinterpret_cast<const int32_t *>(base + o_act);
-        if (svc_in) {
-            HIP_TRY(env, hipMemcpyAsync(base + o_svc, svc_in, svc_b, hipMemcpyHostToDevice, env->stream));
-            d_svc = reinterpret_cast<const double *>(base + o_svc);
-        }
-    }
-    HIP_TRY(env, hipEventRecord(env->ev0, env->stream));
-    const int rc = with_layout(P, [&](auto UA, auto R32) {     // attenuation and the stored record codec
-        return launch_lds(env, k_action_impact<UA, R32>, dim3(P.batch), lds, env->d_P, (int)n_actions, d_act, d_svc, d_out);
+    Span sp[] = {{impact_out, B * A * kActionImpact * sizeof(double), kOut},                       // staging: impact_out | svc_in | actions
+                 {svc_in, B * P.capacity * kServiceQot * sizeof(double), kIn}, {actions, B * A * sizeof(int32_t), kIn}};
+    int rc;
+    if ((rc = stage_open(env, env->stage[kStageImpact], sp))) return rc;
+    rc = timed_launch(env, [&] {
+        return with_layout(P, [&](auto UA, auto R32) {     // attenuation and the stored record codec
+            return launch_lds(env, k_action_impact<UA, R32>, dim3(P.batch), lds, env->d_P, (int)n_actions,
+                              sp[2].as<const int32_t>(), sp[1].as<const double>(), sp[0].as<double>());
+        });
     });
-    if (rc) return rc;
-    HIP_TRY(env, hipEventRecord(env->ev1, env->stream));
-    env->timed = true;
-    if (!env->cfg.io_device) {
-        HIP_TRY(env, hipMemcpyAsync(impact_out, d_out, out_b, hipMemcpyDeviceToHost, env->stream));
-        HIP_TRY(env, hipStreamSynchronize(env->stream));
-    }
-    return ONGYM_OK;
+    return rc ? rc : stage_close(env, sp);
 }
 
 int ongym_sample_actions(ongym_env *env, const uint8_t *mask, uint64_t seed, uint64_t draw_index, int32_t *actions) {

@@ -10,6 +10,10 @@
 
 using ongym::Params;
 
+// Device staging of one analysis call with host buffers: the call's arrays side by side, grown on demand and never shrunk
+struct Stage { void *base; size_t bytes; };
+enum { kStageBlocks, kStageMetrics, kStageQot, kStageImpact, kStages };   // ongym_observe_blocks, _link_metrics, _service_qot, _action_impact
+
 struct ongym_env {
     ongym_config cfg{};
     Params P{};
@@ -25,10 +29,7 @@ struct ongym_env {
     ongym_step_rec *d_out = nullptr; size_t d_out_n = 0;
     int32_t *d_actions = nullptr; int32_t *d_act_out = nullptr; uint8_t *d_flag_out = nullptr; uint8_t *d_mask = nullptr;
     float *d_obs = nullptr; uint8_t *d_obsmask = nullptr;   // lazily allocated staging for ongym_observe with host buffers
-    void *d_blocks = nullptr; size_t d_blocks_bytes = 0;    // staging of ongym_observe_blocks with host buffers (grown on demand)
-    void *d_metrics = nullptr; size_t d_metrics_bytes = 0;  // staging of ongym_link_metrics with host buffers (grown on demand)
-    void *d_qot = nullptr; size_t d_qot_bytes = 0;          // staging of ongym_service_qot with host buffers (grown on demand)
-    void *d_impact = nullptr; size_t d_impact_bytes = 0;    // staging of ongym_action_impact with host buffers (grown on demand)
+    Stage stage[kStages] = {};      // one buffer per analysis call, used with host buffers only (stage_open, ongym_hip.hip)
     int32_t *d_scratch_i = nullptr; size_t scratch_i_bytes = 0; double *d_scratch_d = nullptr;
     void *h_pinned = nullptr; size_t h_pinned_bytes = 0;     // pinned staging of ongym_step_actions_bundle
     bool has_source = false;

@@ -120,13 +120,7 @@ __global__ __launch_bounds__(64) void k_action_impact(const Params *__restrict__
     extern __shared__ __align__(16) unsigned char smem[];
     const Params &P = *Pp;
     Ctx c(P);
-    c.lane = threadIdx.x;
-    c.replica = blockIdx.x;
-    c.lane_terms = 0;
-    c.gn_evals = 0;
-    c.gn_skips = 0;
-    c.paths_tried = 0; c.path_hops = 0; c.active_sum = 0;
-    ctx_bind(c, smem);
+    ctx_open(c, smem, blockIdx.x);
     double *lim0 = reinterpret_cast<double *>(smem + lds_bytes(P));
     double *rlim0 = lim0 + 8, *thr0 = rlim0 + 8, *bef = thr0 + 8;
     const int C = P.capacity, K = P.k_paths, lane = c.lane;
@@ -179,16 +173,7 @@ __global__ __launch_bounds__(64) void k_action_impact(const Params *__restrict__
             if (R32) { ym0 = (uint32_t)uniform_i32((int)ay); ym1 = 0; }
             else { ym0 = G(P.path_mask)[2 * py]; ym1 = G(P.path_mask)[2 * py + 1]; }
             if (!uniform_i32(((ym0 & um0) | (ym1 & um1)) != 0)) continue;
-            const int sy = uniform_i32(rec_slot<R32>(ay, by)), ny = uniform_i32(rec_n<R32>(ay, by));
-            const PathRef p = load_path(c, py);
-            int L;
-            if (P.track_ids) {                       // iy and every running namesake (quirk Q12), as k_service_qot
-                c.skip_id = uniform_i32((int)c.sq[iy]);
-                L = gn_build_list<R32>(c, p.m0, p.m1);
-            } else {
-                L = gn_build_list<R32, true>(c, p.m0, p.m1, iy);
-            }
-            const GnLin g = gn_eval<UA, R32>(c, p, L, sy, ny, coef_for_slots(c, ny));
+            const GnLin g = gn_running<UA, R32>(c, iy);
             if (lane == 0) bef[iy] = g.ase + g.nli;
         }
     }

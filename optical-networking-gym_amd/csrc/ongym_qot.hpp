@@ -44,19 +44,32 @@ __device__ __forceinline__ uint32_t f32_key(float f) {
 }
 __device__ __forceinline__ float key_f32(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
 
+// Linear ASE / NLI of running record iy (wave-uniform) at its own path, slot and slot count against every other running record
+// of the replica: iy itself is left out of the interferer list; with id tracking, iy and every running namesake (quirk Q12),
+// as gn_service_acc skips them
+template <bool UA, bool R32>
+__device__ __forceinline__ GnLin gn_running(Ctx &c, int iy) {
+    const uint32_t ay = c.sa[iy], by = c.sb[iy];
+    const int py = uniform_i32(rec_path<R32>(ay, by)), sy = uniform_i32(rec_slot<R32>(ay, by));
+    const int ny = uniform_i32(rec_n<R32>(ay, by));
+    const PathRef p = load_path(c, py);
+    int L;
+    if (c.P.track_ids) {
+        c.skip_id = uniform_i32((int)c.sq[iy]);
+        L = gn_build_list<R32>(c, p.m0, p.m1);
+    } else {
+        L = gn_build_list<R32, true>(c, p.m0, p.m1, iy);
+    }
+    return gn_eval<UA, R32>(c, p, L, sy, ny, coef_for_slots(c, ny));
+}
+
 template <bool UA, bool R32>
 __global__ __launch_bounds__(64) void k_service_qot(const Params *__restrict__ Pp, double *svc_out, double *replica_out,
                                                     float *link_out) {
     extern __shared__ __align__(16) unsigned char smem[];
     const Params &P = *Pp;
     Ctx c(P);
-    c.lane = threadIdx.x;
-    c.replica = blockIdx.x;
-    c.lane_terms = 0;
-    c.gn_evals = 0;
-    c.gn_skips = 0;
-    c.paths_tried = 0; c.path_hops = 0; c.active_sum = 0;
-    ctx_bind(c, smem);
+    ctx_open(c, smem, blockIdx.x);
     double *lim0 = reinterpret_cast<double *>(smem + lds_bytes(P));
     uint32_t *lcnt = reinterpret_cast<uint32_t *>(lim0 + 8), *lbel = lcnt + P.n_links, *lmin = lbel + P.n_links;
     const int E = P.n_links, C = P.capacity, lane = c.lane;
@@ -71,19 +84,7 @@ __global__ __launch_bounds__(64) void k_service_qot(const Params *__restrict__ P
         double la = 1.0, ln = 1.0;   // linear ASE / NLI of record base + lane
         const int nb = min(kWave, active - base);
         for (int j = 0; j < nb; j++) {
-            const int iy = base + j;
-            const uint32_t ay = c.sa[iy], by = c.sb[iy];
-            const int py = uniform_i32(rec_path<R32>(ay, by)), sy = uniform_i32(rec_slot<R32>(ay, by));
-            const int ny = uniform_i32(rec_n<R32>(ay, by));
-            const PathRef p = load_path(c, py);
-            int L;
-            if (P.track_ids) {                       // iy and every running namesake (quirk Q12), as gn_service_acc skips them
-                c.skip_id = uniform_i32((int)c.sq[iy]);
-                L = gn_build_list<R32>(c, p.m0, p.m1);
-            } else {
-                L = gn_build_list<R32, true>(c, p.m0, p.m1, iy);
-            }
-            const GnLin g = gn_eval<UA, R32>(c, p, L, sy, ny, coef_for_slots(c, ny));
+            const GnLin g = gn_running<UA, R32>(c, base + j);
             if (lane == j) { la = g.ase; ln = g.nli; }
         }
         const int i = base + lane;                                           // < C: capacity is a multiple of 64

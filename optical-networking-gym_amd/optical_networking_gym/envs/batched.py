@@ -73,6 +73,17 @@ class BatchedQRMSAEnv:
         if rc != 0:
             raise OngymError(f"{what} failed ({rc}): {self.lib.ongym_last_error(self._h).decode()}")
 
+    @staticmethod
+    def _check_tensor(t, name: str, dtype, shape, dev, what: Optional[str] = None, align: Optional[int] = None):
+        """A torch tensor the library gets as a device pointer: its type, dtype, shape, contiguity and device, then its alignment
+        (`align` bytes; None: its element size).  `what` words the tensor in the message where the default does not."""
+        import torch
+        if (not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous()
+                or t.device != dev):
+            raise ValueError(f"{name} must be a contiguous {what or f'{dtype} tensor of shape {shape}'} on {dev}")
+        if t.data_ptr() % (align or t.element_size()):
+            raise ValueError(f"{name} must be {f'{align}-byte aligned' if align else 'aligned to its element size'}")
+
     @property
     def reject_action(self) -> int:
         return self.holder.reject_action
@@ -206,11 +217,7 @@ class BatchedQRMSAEnv:
                 raise ValueError("out must be a tuple (obs, mask, action_map)")
             dev = rl._device(self)
             for t, name, dt, shape in zip(out, ("obs", "mask", "action_map"), (torch.float32, torch.uint8, torch.int32), shapes):
-                if (not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous()
-                        or t.device != dev):
-                    raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on {dev}")
-                if t.data_ptr() % 4:
-                    raise ValueError(f"{name} must be 4-byte aligned")
+                self._check_tensor(t, name, dt, shape, dev, align=4)
             rl._check_stream(self)
             self._check(self.lib.ongym_observe_blocks(self._h, J, *(C.c_void_p(t.data_ptr()) for t in out)),
                         "ongym_observe_blocks")
@@ -261,11 +268,7 @@ class BatchedQRMSAEnv:
             if link_stats is not None:
                 named.append((link_stats, "link_stats", torch.float64, shapes[2]))
             for t, name, dt, shape in named:
-                if (not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous()
-                        or t.device != dev):
-                    raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on {dev}")
-                if t.data_ptr() % t.element_size():
-                    raise ValueError(f"{name} must be aligned to its element size")
+                self._check_tensor(t, name, dt, shape, dev)
             rl._check_stream(self)
             ptrs = [C.c_void_p(t.data_ptr()) for t in out] + [C.c_void_p(link_stats.data_ptr() if link_stats is not None else None)]
             self._check(self.lib.ongym_link_metrics(self._h, *ptrs), "ongym_link_metrics")
@@ -304,13 +307,8 @@ class BatchedQRMSAEnv:
                 raise ValueError("out: at least one of svc, replica, link must be a tensor")
             dev = rl._device(self)
             for t, name, dt, shape in zip(out, ("svc", "replica", "link"), (torch.float64, torch.float64, torch.float32), shapes):
-                if t is None:
-                    continue
-                if (not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous()
-                        or t.device != dev):
-                    raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on {dev}")
-                if t.data_ptr() % t.element_size():
-                    raise ValueError(f"{name} must be aligned to its element size")
+                if t is not None:
+                    self._check_tensor(t, name, dt, shape, dev)
             rl._check_stream(self)
             ptrs = [C.c_void_p(t.data_ptr() if t is not None else None) for t in out]
             self._check(self.lib.ongym_service_qot(self._h, *ptrs), "ongym_service_qot")
@@ -350,13 +348,8 @@ class BatchedQRMSAEnv:
                 raise ValueError("an io_device environment needs out, a float64 tensor of shape (B, A, 8)")
             shape = (B, A, len(nat.ACTION_IMPACT))
             for t, name, sh in ((out, "out", shape), (svc, "svc", svc_shape)):
-                if t is None:
-                    continue
-                if (not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or tuple(t.shape) != sh or not t.is_contiguous()
-                        or t.device != dev):
-                    raise ValueError(f"{name} must be a contiguous torch.float64 tensor of shape {sh} on {dev}")
-                if t.data_ptr() % t.element_size():
-                    raise ValueError(f"{name} must be aligned to its element size")
+                if t is not None:
+                    self._check_tensor(t, name, torch.float64, sh, dev)
             if actions.data_ptr() % 4:
                 raise ValueError("actions must be aligned to its element size")
             rl._check_stream(self)
@@ -484,12 +477,7 @@ class BatchedQRMSAEnv:
         if self.holder.struct.io_device:
             import torch
             from .. import rl
-            dev = rl._device(self)
-            if (not isinstance(blob, torch.Tensor) or blob.dtype != torch.uint8 or blob.dim() != 1 or blob.numel() != nbytes
-                    or not blob.is_contiguous() or blob.device != dev):
-                raise ValueError(f"{what} must be a contiguous 1-D uint8 tensor of {nbytes} bytes on {dev}")
-            if blob.data_ptr() % 16:
-                raise ValueError(f"{what} must be 16-byte aligned")
+            self._check_tensor(blob, what, torch.uint8, (nbytes,), rl._device(self), f"1-D uint8 tensor of {nbytes} bytes", 16)
             return C.c_void_p(blob.data_ptr())
         if (not isinstance(blob, np.ndarray) or blob.dtype != np.uint8 or blob.ndim != 1 or blob.size != nbytes
                 or not blob.flags.c_contiguous or (writable and not blob.flags.writeable)):
@@ -549,12 +537,7 @@ class BatchedQRMSAEnv:
         if self.holder.struct.io_device:
             import torch
             from .. import rl
-            dev = rl._device(self)
-            if (not isinstance(src, torch.Tensor) or src.dtype != torch.int32 or tuple(src.shape) != (B,)
-                    or not src.is_contiguous() or src.device != dev):
-                raise ValueError(f"src must be a contiguous int32 [{B}] tensor on {dev}")
-            if src.data_ptr() % 4:
-                raise ValueError("src must be 4-byte aligned")
+            self._check_tensor(src, "src", torch.int32, (B,), rl._device(self), f"int32 [{B}] tensor", 4)
             rl._check_stream(self)
             self._check(self.lib.ongym_fork(self._h, C.c_void_p(src.data_ptr()), flags), "ongym_fork")
             return
