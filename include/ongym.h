@@ -15,6 +15,9 @@
  *             ONGYM_F_QOT_ERROR flag of ongym_step_rec.flags (the Python shim re-raises it in single-env mode).
  * Threading : one ongym_env = one HIP device + one HIP stream; not thread-safe; launches are asynchronous on that
  *             stream, results are complete after ongym_sync() (calls that copy to host buffers sync themselves).
+ * Staging   : a call that takes host buffers lays its arrays out in a device buffer of its call family (grown on demand,
+ *             kept until ongym_destroy), copies the inputs in, launches, copies the outputs back and synchronises once.
+ *             A NULL optional array takes no room.  With cfg.io_device the kernels get the caller's pointers instead.
  * Multi-GPU : one process per GPU, one ongym_env each; replicas are independent so there is no data-path collective.
  */
 #ifndef ONGYM_H
@@ -242,7 +245,8 @@ int ongym_seed_base(ongym_env *env, uint64_t seed, uint64_t replica_base);
  * Used for parity against captured reference traces (each _next_service call consumes one entry). */
 int ongym_set_requests(ongym_env *env, const ongym_request *reqs, int64_t n_per_replica);
 
-/* QRMSAEnv.reset (qrmsa.pyx:427-504) on the replicas with mask[r] != 0 (NULL = all). */
+/* QRMSAEnv.reset (qrmsa.pyx:427-504) on the replicas with mask[r] != 0 (NULL = all).  The mask is read on the stream (a
+ * host mask is copied at the call) and the call returns without synchronising; so does ongym_reset_episode_counters. */
 int ongym_reset(ongym_env *env, const uint8_t *mask);
 
 /* QRMSAEnv.reset(options={"only_episode_counters": True}) (qrmsa.pyx:427-464) on the replicas with mask[r] != 0 (NULL =
@@ -450,10 +454,11 @@ int ongym_masked_categorical_backward_rows(ongym_env *env, int32_t rows, const v
 int ongym_gae(ongym_env *env, int32_t steps, const ongym_step_rec *recs, const float *values,
               const float *last_values, float gamma, float gae_lambda, float *advantages, float *returns);
 
-/* Plugin-API queries on one replica (host buffers always): */
+/* Plugin-API queries on one replica (host buffers always, staged with cfg.io_device too; each synchronises once): */
 /* QRMSAEnv.get_available_slots(path) (qrmsa.pyx:1482-1512): out[n_slots], 1 = free on every link of the path */
 int ongym_query_available(ongym_env *env, int32_t replica, int32_t path_id, int32_t *out);
-/* calculate_osnr(env, service) (core/osnr.pyx:21-142) for a candidate (path, slot, nslots): out = gsnr, ase, nli dB */
+/* calculate_osnr(env, service) (core/osnr.pyx:21-142) for a candidate (path, slot, nslots): out = gsnr, ase, nli dB
+ * (ongym_query_gsnr_many with one candidate) */
 int ongym_query_gsnr(ongym_env *env, int32_t replica, int32_t path_id, int32_t slot, int32_t nslots, double out[3]);
 /* The same for `count` candidates of one replica in ONE launch (one wavefront per candidate) — what a plugin heuristic
  * that scores every feasible start needs (heuristics.py:272-328, 330-416, 647-749): cands int32 [count][3] =

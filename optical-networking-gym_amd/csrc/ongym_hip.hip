@@ -265,11 +265,13 @@ __global__ __launch_bounds__(64) void k_query_gsnr_many(const Params *__restrict
     if (c.lane == 0) { out[3 * blockIdx.x] = g[0]; out[3 * blockIdx.x + 1] = g[1]; out[3 * blockIdx.x + 2] = g[2]; }
 }
 
-enum { kQAvailable = 0, kQGsnr = 1, kQGrid = 2, kQServices = 3, kQRequest = 4, kQCandidates = 5, kQPathFree = 6 };
+enum { kQAvailable, kQGrid, kQServices, kQRequest, kQCandidates, kQPathFree };
 
+// One wavefront answers one plugin-API query on one replica.  Each case has its own typed arguments: `row` (kQCandidates: the
+// caller's row), `out_i` (flags per slot, the grid's bits, one flag, or the service count), `svc`, `req`; the others are null.
 template <bool UA, bool R32>
 __global__ __launch_bounds__(64) void k_query(const Params *__restrict__ Pp, int what, int replica, int path, int slot, int n,
-                                              int32_t *out_i, double *out_d) {
+                                              const int32_t *row, int32_t *out_i, ongym_service *svc, ongym_request *req) {
     extern __shared__ __align__(16) unsigned char smem[];
     const Params &P = *Pp;
     Ctx c(P);
@@ -282,33 +284,24 @@ __global__ __launch_bounds__(64) void k_query(const Params *__restrict__ Pp, int
             uint64_t w = __shfl((unsigned long long)x, j >> 6);
             if (c.lane == 0) out_i[j] = (int32_t)((w >> (j & 63)) & 1ull);
         }
-    } else if (what == kQGsnr) {        // calculate_osnr(env, candidate), core/osnr.pyx:21-142
-        PathRef p = load_path(c, path);
-        int L = gn_build_list<R32>(c, p.m0, p.m1);
-        GnLin lin = gn_eval<UA, R32>(c, p, L, slot, n);
-        double g[3];
-        gn_to_db(lin, g);
-        if (c.lane == 0) { out_d[0] = g[0]; out_d[1] = g[1]; out_d[2] = g[2]; }
     } else if (what == kQGrid) {        // topology.graph["available_slots"]
         for (int i = c.lane; i < P.n_links * P.n_slots; i += kWave) {
             int l = i / P.n_slots, j = i % P.n_slots;
             out_i[i] = (int32_t)((c.occ[l * P.row_words + (j >> 6)] >> (j & 63)) & 1ull);
         }
-    } else if (what == kQServices) {    // running services
-        ongym_service *o = reinterpret_cast<ongym_service *>(out_i + 2);
+    } else if (what == kQServices) {    // running services: the count, then the records
         if (c.lane == 0) out_i[0] = c.active;
         for (int i = c.lane; i < c.active; i += kWave) {
             uint32_t a = c.sa[i], b = c.sb[i];
-            o[i].path_id = rec_path<R32>(a, b); o[i].slot = (int16_t)rec_slot<R32>(a, b);
-            o[i].nslots = (int16_t)rec_n<R32>(a, b); o[i].modulation = (int16_t)rec_mod<R32>(a, b);
-            o[i].reserved = c.sr[i] < 0.f ? 1 : 0;   // 1: in the disrupted list (measure_disruptions)
-            o[i].release_time = fabsf(c.sr[i]);
-            o[i].service_id = P.track_ids ? (int32_t)c.sq[i] : -1; o[i].pad_ = 0;
-            o[i].osnr = P.track_ids ? c.so[i] : 0.0;
+            svc[i].path_id = rec_path<R32>(a, b); svc[i].slot = (int16_t)rec_slot<R32>(a, b);
+            svc[i].nslots = (int16_t)rec_n<R32>(a, b); svc[i].modulation = (int16_t)rec_mod<R32>(a, b);
+            svc[i].reserved = c.sr[i] < 0.f ? 1 : 0;   // 1: in the disrupted list (measure_disruptions)
+            svc[i].release_time = fabsf(c.sr[i]);
+            svc[i].service_id = P.track_ids ? (int32_t)c.sq[i] : -1; svc[i].pad_ = 0;
+            svc[i].osnr = P.track_ids ? c.so[i] : 0.0;
         }
     } else if (what == kQCandidates) {  // _get_candidates on a caller-supplied row: path = total_slots, n = nslots
         const int total = path;
-        const int32_t *row = out_i;         // input row [total], output flags at out_i[1024 .. 1024+total)
         uint64_t x = 0;
         for (int j = 0; j < 64; j++) {
             int sl = c.lane * 64 + j;
@@ -319,7 +312,7 @@ __global__ __launch_bounds__(64) void k_query(const Params *__restrict__ Pp, int
         x = run_and(x, rr, n + 1);
         for (int j = 0; j < 64; j++) {
             int sl = c.lane * 64 + j;
-            if (sl < total) out_i[1024 + sl] = (int32_t)((x >> j) & 1ull);
+            if (sl < total) out_i[sl] = (int32_t)((x >> j) & 1ull);
         }
     } else if (what == kQPathFree) {    // is_path_free, envs/qrmsa.pyx:1248-1264
         PathRef p = load_path(c, path);
@@ -329,9 +322,8 @@ __global__ __launch_bounds__(64) void k_query(const Params *__restrict__ Pp, int
         if (c.lane == 0) out_i[0] = (int32_t)((w >> (slot & 63)) & 1ull);
     } else if (what == kQRequest) {
         if (c.lane == 0) {
-            ongym_request *q = reinterpret_cast<ongym_request *>(out_i);
-            q->arrival_time = c.e->cur_at; q->holding_time = c.e->cur_ht; q->bit_rate = c.e->cur_br;
-            q->source = (int16_t)c.e->cur_src; q->destination = (int16_t)c.e->cur_dst;
+            req->arrival_time = c.e->cur_at; req->holding_time = c.e->cur_ht; req->bit_rate = c.e->cur_br;
+            req->source = (int16_t)c.e->cur_src; req->destination = (int16_t)c.e->cur_dst;
         }
     }
 }
@@ -486,8 +478,8 @@ static int timed_launch(ongym_env *env, F &&f) {
     return 0;
 }
 
-// One array of an analysis call: the caller's pointer (null: an optional array that is not asked for), its size, whether the
-// kernel reads it (kIn), writes it (kOut) or both, and, after stage_open, the pointer the kernel gets.
+// One array of a call: the caller's pointer (null: an optional array that is not asked for), its size, whether the kernel
+// reads it (kIn), writes it (kOut) or both, and, after stage_open, the pointer the kernel gets.
 enum { kIn = 1, kOut = 2 };
 struct Span {
     const void *host; size_t bytes; int dir;
@@ -495,12 +487,13 @@ struct Span {
     template <class T> T *as() const { return static_cast<T *>(dev); }
 };
 
-// Device pointers for the arrays of a call, given in layout order.  With io_device they are the caller's.  Otherwise the arrays
-// lie in `st` at 256-byte offsets (an array that is not asked for takes no room and gets a null pointer, which the kernels
-// branch on), `st` is grown if it is too small, and the kIn arrays are copied in.
+// Device pointers for the arrays of a call, given in layout order.  With io_device they are the caller's, unless the call
+// always takes host buffers (`always`: the queries).  Otherwise the arrays lie in `st` at 256-byte offsets (an array that is not
+// asked for takes no room and gets a null pointer, which the kernels branch on), `st` is grown if it is too small, and the kIn
+// arrays are copied in.
 template <size_t N>
-static int stage_open(ongym_env *env, Stage &st, Span (&sp)[N]) {
-    if (env->cfg.io_device) {
+static int stage_open(ongym_env *env, Stage &st, Span (&sp)[N], bool always = false) {
+    if (env->cfg.io_device && !always) {
         for (Span &s : sp) s.dev = const_cast<void *>(s.host);
         return 0;
     }
@@ -523,25 +516,15 @@ static int stage_open(ongym_env *env, Stage &st, Span (&sp)[N]) {
     return 0;
 }
 
-// After the launch: the kOut arrays back to the caller and one synchronisation (nothing with io_device)
+// After the launch: the kOut arrays back to the caller and one synchronisation (nothing where stage_open staged nothing)
 template <size_t N>
-static int stage_close(ongym_env *env, const Span (&sp)[N]) {
-    if (env->cfg.io_device) return ONGYM_OK;
+static int stage_close(ongym_env *env, const Span (&sp)[N], bool always = false) {
+    if (env->cfg.io_device && !always) return ONGYM_OK;
     for (const Span &s : sp)
         if (s.host && (s.dir & kOut))
             HIP_TRY(env, hipMemcpyAsync(const_cast<void *>(s.host), s.dev, s.bytes, hipMemcpyDeviceToHost, env->stream));
     HIP_TRY(env, hipStreamSynchronize(env->stream));
     return ONGYM_OK;
-}
-
-// The optional reset mask [batch] as the kernels read it: the caller's pointer with io_device, else a device copy
-static int stage_reset_mask(ongym_env *env, const uint8_t *mask, const uint8_t **dmask) {
-    *dmask = mask;
-    if (mask && !env->cfg.io_device) {
-        HIP_TRY(env, hipMemcpyAsync(env->d_mask, mask, (size_t)env->P.batch, hipMemcpyHostToDevice, env->stream));
-        *dmask = env->d_mask;
-    }
-    return 0;
 }
 
 static int build(ongym_env *env, const ongym_config *c) {
@@ -873,14 +856,6 @@ static int build(ongym_env *env, const ongym_config *c) {
         }
         env->err.clear();
     }
-    // scratch for queries / host-buffer I/O
-    env->scratch_i_bytes = std::max(std::max((size_t)E * c->n_slots * 4, (size_t)c->capacity * sizeof(ongym_service) + 16), (size_t)2048 * 4);
-    if ((rc = dev_alloc(env, env->scratch_i_bytes / 4 + 4, &env->d_scratch_i, true))) return rc;
-    if ((rc = dev_alloc(env, 4, &env->d_scratch_d, true))) return rc;
-    if ((rc = dev_alloc(env, B, &env->d_actions, true))) return rc;
-    if ((rc = dev_alloc(env, B, &env->d_act_out, true))) return rc;
-    if ((rc = dev_alloc(env, B, &env->d_flag_out, true))) return rc;
-    if ((rc = dev_alloc(env, B, &env->d_mask, true))) return rc;
 #ifdef ONGYM_STAMPS
     if ((rc = dev_alloc(env, 16, &P.dbg, true))) return rc;
 #endif
@@ -1112,7 +1087,6 @@ void ongym_destroy(ongym_env *env) {
     if (env->stream) (void)hipStreamSynchronize(env->stream);
     for (void *p : env->allocs) (void)hipFree(p);
     if (env->d_trace) (void)hipFree(env->d_trace);
-    if (env->d_out) (void)hipFree(env->d_out);
     if (env->h_pinned) (void)hipHostFree(env->h_pinned);
     if (env->d_state_stage) (void)hipFree(env->d_state_stage);
     for (Stage &st : env->stage) if (st.base) (void)hipFree(st.base);
@@ -1230,13 +1204,15 @@ int ongym_set_requests(ongym_env *env, const ongym_request *reqs, int64_t n_per_
     return ONGYM_OK;
 }
 
+// The two resets return without synchronising: they open a stage for the optional mask [batch] (a host mask is copied in on the
+// stream, a NULL one reaches the kernel as NULL) and never close it.
 int ongym_reset(ongym_env *env, const uint8_t *mask) {
     if (!env) return ONGYM_E_ARG;
     if (!env->has_source) return need_source(env);
     HIP_TRY(env, hipSetDevice(env->cfg.device));
-    const uint8_t *dmask;
-    if (int rc = stage_reset_mask(env, mask, &dmask)) return rc;
-    return launch_lds(env, k_reset, dim3(env->P.batch), env->lds, env->d_P, dmask);
+    Span sp[] = {{mask, (size_t)env->P.batch, kIn}};
+    if (int rc = stage_open(env, env->stage[kStageReset], sp)) return rc;
+    return launch_lds(env, k_reset, dim3(env->P.batch), env->lds, env->d_P, sp[0].as<const uint8_t>());
 }
 
 int ongym_reset_episode_counters(ongym_env *env, const uint8_t *mask) {
@@ -1247,32 +1223,24 @@ int ongym_reset_episode_counters(ongym_env *env, const uint8_t *mask) {
         return ONGYM_E_STATE;
     }
     HIP_TRY(env, hipSetDevice(env->cfg.device));
-    const uint8_t *dmask;
-    if (int rc = stage_reset_mask(env, mask, &dmask)) return rc;
+    Span sp[] = {{mask, (size_t)env->P.batch, kIn}};
+    if (int rc = stage_open(env, env->stage[kStageReset], sp)) return rc;
     int threads = 64, blocks = (env->P.batch + threads - 1) / threads;
-    hipLaunchKernelGGL(k_reset_counters, dim3(blocks), dim3(threads), 0, env->stream, env->P, dmask);
+    hipLaunchKernelGGL(k_reset_counters, dim3(blocks), dim3(threads), 0, env->stream, env->P, sp[0].as<const uint8_t>());
     HIP_TRY(env, hipGetLastError());
     return ONGYM_OK;
 }
 
-static int launch_run(ongym_env *env, int mode, int policy, int nsteps, const int32_t *d_actions, int32_t *d_act_out,
-                      uint8_t *d_flag_out, ongym_step_rec *d_out) {
+static int launch_run(ongym_env *env, int mode, int policy, int nsteps, const int32_t *actions, int32_t *act_out,
+                      uint8_t *flag_out, ongym_step_rec *out) {
     // the lean kernels: same results, half the issued instructions (ongym_fast.hpp)
     const LeanFns *lean = mode == kModePolicyStep ? lean_unit(env, policy) : nullptr;
     return timed_launch(env, [&] {
-        return lean ? lean->launch(env, nsteps, d_out) : with_run_kernel(env, policy, [&](auto kernel, size_t lds) {
-            return launch_lds(env, kernel, dim3(env->P.batch), lds, env->d_P, mode, nsteps, d_actions, d_act_out, d_flag_out,
-                              d_out, policy);
+        return lean ? lean->launch(env, nsteps, out) : with_run_kernel(env, policy, [&](auto kernel, size_t lds) {
+            return launch_lds(env, kernel, dim3(env->P.batch), lds, env->d_P, mode, nsteps, actions, act_out, flag_out, out,
+                              policy);
         });
     });
-}
-
-static int ensure_out(ongym_env *env, size_t n) {
-    if (env->d_out_n >= n) return 0;
-    if (env->d_out) { (void)hipFree(env->d_out); env->d_out = nullptr; env->d_out_n = 0; }
-    HIP_TRY(env, hipMalloc(reinterpret_cast<void **>(&env->d_out), n * sizeof(ongym_step_rec)));
-    env->d_out_n = n;
-    return 0;
 }
 
 static int check_policy(ongym_env *env, int32_t policy) {
@@ -1293,31 +1261,23 @@ int ongym_step_policy(ongym_env *env, int32_t policy, int32_t nsteps, ongym_step
     if (nsteps <= 0) return fail_arg(env, "nsteps must be positive");
     if (!env->has_source) return need_source(env);
     HIP_TRY(env, hipSetDevice(env->cfg.device));
-    if (out && !env->cfg.io_device) {
-        size_t n = (size_t)nsteps * env->P.batch;
-        if ((rc = ensure_out(env, n))) return rc;
-        if ((rc = launch_run(env, kModePolicyStep, policy, nsteps, nullptr, nullptr, nullptr, env->d_out))) return rc;
-        HIP_TRY(env, hipMemcpyAsync(out, env->d_out, n * sizeof(ongym_step_rec), hipMemcpyDeviceToHost, env->stream));
-        HIP_TRY(env, hipStreamSynchronize(env->stream));
-        return ONGYM_OK;
-    }
-    return launch_run(env, kModePolicyStep, policy, nsteps, nullptr, nullptr, nullptr, out);
+    Span sp[] = {{out, (size_t)nsteps * env->P.batch * sizeof(ongym_step_rec), kOut}};
+    if ((rc = stage_open(env, env->stage[kStageStep], sp))) return rc;
+    rc = launch_run(env, kModePolicyStep, policy, nsteps, nullptr, nullptr, nullptr, sp[0].as<ongym_step_rec>());
+    return rc || !out ? rc : stage_close(env, sp);     // without records nothing comes back: the call only launches
 }
 
 int ongym_step_actions(ongym_env *env, const int32_t *actions, ongym_step_rec *out) {
     if (!env || !actions) return env ? fail_arg(env, "null actions") : ONGYM_E_ARG;
     if (!env->has_source) return need_source(env);
     HIP_TRY(env, hipSetDevice(env->cfg.device));
+    const size_t B = (size_t)env->P.batch;
+    Span sp[] = {{out, B * sizeof(ongym_step_rec), kOut}, {actions, B * sizeof(int32_t), kIn}};
     int rc;
-    if (env->cfg.io_device) return launch_run(env, kModeActionStep, ONGYM_POLICY_FIRST_FIT, 1, actions, nullptr, nullptr, out);
-    HIP_TRY(env, hipMemcpyAsync(env->d_actions, actions, (size_t)env->P.batch * 4, hipMemcpyHostToDevice, env->stream));
-    if (out) {
-        if ((rc = ensure_out(env, (size_t)env->P.batch))) return rc;
-        if ((rc = launch_run(env, kModeActionStep, ONGYM_POLICY_FIRST_FIT, 1, env->d_actions, nullptr, nullptr, env->d_out))) return rc;
-        HIP_TRY(env, hipMemcpyAsync(out, env->d_out, (size_t)env->P.batch * sizeof(ongym_step_rec), hipMemcpyDeviceToHost, env->stream));
-    } else if ((rc = launch_run(env, kModeActionStep, ONGYM_POLICY_FIRST_FIT, 1, env->d_actions, nullptr, nullptr, nullptr))) return rc;
-    HIP_TRY(env, hipStreamSynchronize(env->stream));
-    return ONGYM_OK;
+    if ((rc = stage_open(env, env->stage[kStageStep], sp))) return rc;
+    rc = launch_run(env, kModeActionStep, ONGYM_POLICY_FIRST_FIT, 1, sp[1].as<const int32_t>(), nullptr, nullptr,
+                    sp[0].as<ongym_step_rec>());
+    return rc ? rc : stage_close(env, sp);
 }
 
 int ongym_step_actions_bundle(ongym_env *env, const int32_t *actions, int32_t next_policy, ongym_step_rec *rec_out,
@@ -1352,19 +1312,20 @@ int ongym_step_actions_bundle(ongym_env *env, const int32_t *actions, int32_t ne
                             reinterpret_cast<ongym_step_rec *>(hp + o_rec));
         if (rc) return rc;
         HIP_TRY(env, hipMemcpyAsync(hp + o_env, env->P.env, B * sizeof(DevEnv), hipMemcpyDeviceToHost, env->stream));
+        HIP_TRY(env, hipStreamSynchronize(env->stream));
     } else {
-        if ((rc = ensure_out(env, B))) return rc;
-        HIP_TRY(env, hipMemcpyAsync(env->d_actions, actions, B * 4, hipMemcpyHostToDevice, env->stream));
-        if ((rc = launch_run(env, kModeActionStep, ONGYM_POLICY_FIRST_FIT, 1, env->d_actions, nullptr, nullptr, env->d_out))) return rc;
-        if (next_policy >= 0 && (rc = launch_run(env, kModePolicyOnly, next_policy, 1, nullptr, env->d_act_out, env->d_flag_out, nullptr))) return rc;
-        HIP_TRY(env, hipMemcpyAsync(hp + o_rec, env->d_out, B * sizeof(ongym_step_rec), hipMemcpyDeviceToHost, env->stream));
+        // many replicas: device buffers from the step calls' stage; stage_close copies into the pinned buffer and synchronises
+        const bool next = next_policy >= 0;
+        Span sp[] = {{hp + o_rec, B * sizeof(ongym_step_rec), kOut}, {actions, B * sizeof(int32_t), kIn},
+                     {next ? hp + o_act : nullptr, B * sizeof(int32_t), kOut}, {next ? hp + o_flag : nullptr, B, kOut}};
+        if ((rc = stage_open(env, env->stage[kStageStep], sp))) return rc;
+        if ((rc = launch_run(env, kModeActionStep, ONGYM_POLICY_FIRST_FIT, 1, sp[1].as<const int32_t>(), nullptr, nullptr,
+                             sp[0].as<ongym_step_rec>()))) return rc;
+        if (next && (rc = launch_run(env, kModePolicyOnly, next_policy, 1, nullptr, sp[2].as<int32_t>(), sp[3].as<uint8_t>(),
+                                     nullptr))) return rc;
         HIP_TRY(env, hipMemcpyAsync(hp + o_env, env->P.env, B * sizeof(DevEnv), hipMemcpyDeviceToHost, env->stream));
-        if (next_policy >= 0) {
-            HIP_TRY(env, hipMemcpyAsync(hp + o_act, env->d_act_out, B * 4, hipMemcpyDeviceToHost, env->stream));
-            HIP_TRY(env, hipMemcpyAsync(hp + o_flag, env->d_flag_out, B, hipMemcpyDeviceToHost, env->stream));
-        }
+        if ((rc = stage_close(env, sp))) return rc;
     }
-    HIP_TRY(env, hipStreamSynchronize(env->stream));
     memcpy(rec_out, hp + o_rec, B * sizeof(ongym_step_rec));
     const DevEnv *de = reinterpret_cast<const DevEnv *>(hp + o_env);
     int flags = 0;
@@ -1389,29 +1350,17 @@ int ongym_observe(ongym_env *env, float *obs, uint8_t *mask) {
     const size_t obs_dim = 3 + P.k_paths + (size_t)P.k_paths * P.n_mods_consider * 12;
     const size_t nact = (size_t)P.k_paths * P.n_mods_consider * P.n_slots + 1;
     const size_t B = (size_t)P.batch;
-    float *d_obs = obs; uint8_t *d_mask = mask;
-    if (!env->cfg.io_device) {
-        if (!env->d_obs) {
-            HIP_TRY(env, hipMalloc(reinterpret_cast<void **>(&env->d_obs), B * obs_dim * sizeof(float)));
-            env->allocs.push_back(env->d_obs);
-            HIP_TRY(env, hipMalloc(reinterpret_cast<void **>(&env->d_obsmask), B * nact));
-            env->allocs.push_back(env->d_obsmask);
-        }
-        d_obs = env->d_obs; d_mask = env->d_obsmask;
-    }
-    HIP_TRY(env, hipMemsetAsync(d_mask, 0, B * nact, env->stream));     // k_observe only sets the ones
-    const int rc = timed_launch(env, [&] {
+    Span sp[] = {{mask, B * nact, kOut}, {obs, B * obs_dim * sizeof(float), kOut}};               // staging: mask | obs
+    int rc;
+    if ((rc = stage_open(env, env->stage[kStageMask], sp))) return rc;
+    HIP_TRY(env, hipMemsetAsync(sp[0].dev, 0, B * nact, env->stream));     // k_observe only sets the ones
+    rc = timed_launch(env, [&] {
         return with_layout(P, [&](auto UA, auto R32) {
-            return launch_lds(env, k_observe<UA, R32>, dim3(P.batch), obs_layout(P).total, env->d_P, d_obs, d_mask);
+            return launch_lds(env, k_observe<UA, R32>, dim3(P.batch), obs_layout(P).total, env->d_P, sp[1].as<float>(),
+                              sp[0].as<uint8_t>());
         });
     });
-    if (rc) return rc;
-    if (!env->cfg.io_device) {
-        HIP_TRY(env, hipMemcpyAsync(obs, d_obs, B * obs_dim * sizeof(float), hipMemcpyDeviceToHost, env->stream));
-        HIP_TRY(env, hipMemcpyAsync(mask, d_mask, B * nact, hipMemcpyDeviceToHost, env->stream));
-        HIP_TRY(env, hipStreamSynchronize(env->stream));
-    }
-    return ONGYM_OK;
+    return rc ? rc : stage_close(env, sp);
 }
 
 int ongym_observe_blocks(ongym_env *env, int32_t blocks, float *obs, uint8_t *mask, int32_t *action_map) {
@@ -1504,24 +1453,12 @@ int ongym_sample_actions(ongym_env *env, const uint8_t *mask, uint64_t seed, uin
     HIP_TRY(env, hipSetDevice(env->cfg.device));
     const Params &P = env->P;
     const size_t nact = (size_t)P.k_paths * P.n_mods_consider * P.n_slots + 1, B = (size_t)P.batch;
-    const uint8_t *d_mask = mask;
-    int32_t *d_act = actions;
-    if (!env->cfg.io_device) {
-        if (!env->d_obsmask) {
-            HIP_TRY(env, hipMalloc(reinterpret_cast<void **>(&env->d_obsmask), B * nact));
-            env->allocs.push_back(env->d_obsmask);
-        }
-        HIP_TRY(env, hipMemcpyAsync(env->d_obsmask, mask, B * nact, hipMemcpyHostToDevice, env->stream));
-        d_mask = env->d_obsmask; d_act = env->d_act_out;
-    }
-    hipLaunchKernelGGL(k_sample_mask, dim3(P.batch), dim3(64), 0, env->stream, d_mask, (long long)nact, seed, env->replica_base,
-                       draw_index, d_act);
+    Span sp[] = {{mask, B * nact, kIn}, {actions, B * sizeof(int32_t), kOut}};                     // staging: mask | actions
+    if (int rc = stage_open(env, env->stage[kStageMask], sp)) return rc;
+    hipLaunchKernelGGL(k_sample_mask, dim3(P.batch), dim3(64), 0, env->stream, sp[0].as<const uint8_t>(), (long long)nact, seed,
+                       env->replica_base, draw_index, sp[1].as<int32_t>());
     HIP_TRY(env, hipGetLastError());
-    if (!env->cfg.io_device) {
-        HIP_TRY(env, hipMemcpyAsync(actions, d_act, B * 4, hipMemcpyDeviceToHost, env->stream));
-        HIP_TRY(env, hipStreamSynchronize(env->stream));
-    }
-    return ONGYM_OK;
+    return stage_close(env, sp);
 }
 
 // Masked categorical action head (csrc/ongym_policy_head.hpp): one wavefront per row, kHeadWaves rows per workgroup.
@@ -1644,43 +1581,43 @@ int ongym_policy_actions(ongym_env *env, int32_t policy, int32_t *actions, uint8
     int rc;
     if ((rc = check_policy(env, policy))) return rc;
     HIP_TRY(env, hipSetDevice(env->cfg.device));
-    if (env->cfg.io_device) return launch_run(env, kModePolicyOnly, policy, 1, nullptr, actions, flags, nullptr);
-    if ((rc = launch_run(env, kModePolicyOnly, policy, 1, nullptr, env->d_act_out, env->d_flag_out, nullptr))) return rc;
-    HIP_TRY(env, hipMemcpyAsync(actions, env->d_act_out, (size_t)env->P.batch * 4, hipMemcpyDeviceToHost, env->stream));
-    if (flags) HIP_TRY(env, hipMemcpyAsync(flags, env->d_flag_out, (size_t)env->P.batch, hipMemcpyDeviceToHost, env->stream));
-    HIP_TRY(env, hipStreamSynchronize(env->stream));
-    return ONGYM_OK;
+    const size_t B = (size_t)env->P.batch;
+    Span sp[] = {{actions, B * sizeof(int32_t), kOut}, {flags, B, kOut}};
+    if ((rc = stage_open(env, env->stage[kStagePolicy], sp))) return rc;
+    rc = launch_run(env, kModePolicyOnly, policy, 1, nullptr, sp[0].as<int32_t>(), sp[1].as<uint8_t>(), nullptr);
+    return rc ? rc : stage_close(env, sp);
 }
 
-static int query(ongym_env *env, int what, int replica, int path, int slot, int n) {
+// One plugin-API query: range checks, k_query, the results back behind one synchronisation.  sp = the int32 row that goes in,
+// the int32 results, the service records, the request; a query leaves empty what it does not use.  The results are host buffers
+// under io_device too, so the query stage is always used.
+enum { kSpanRow, kSpanInt, kSpanSvc, kSpanReq, kQuerySpans };
+static int query(ongym_env *env, int what, int replica, int path, int slot, int n, Span (&sp)[kQuerySpans]) {
     if (replica < 0 || replica >= env->P.batch) return fail_arg(env, "replica out of range");
-    if ((what == kQAvailable || what == kQGsnr || what == kQPathFree) && (path < 0 || path >= env->P.n_paths)) return fail_arg(env, "path id out of range");
-    if (what == kQGsnr && (slot < 0 || n <= 0 || slot + n > env->P.n_slots)) return fail_arg(env, "slot range out of the grid");
+    if ((what == kQAvailable || what == kQPathFree) && (path < 0 || path >= env->P.n_paths)) return fail_arg(env, "path id out of range");
     if (what == kQPathFree && (slot < 0 || n <= 0 || slot >= env->P.n_slots || n > 1023)) return fail_arg(env, "slot / nslots out of range");
     if (what == kQCandidates && (path <= 0 || path > 1023 || n <= 0 || n > 1023)) return fail_arg(env, "total_slots / nslots out of range");
     HIP_TRY(env, hipSetDevice(env->cfg.device));
-    return with_layout(env->P, [&](auto UA, auto R32) {
-        return launch_lds(env, k_query<UA, R32>, dim3(1), env->lds, env->d_P, what, replica, path, slot, n, env->d_scratch_i,
-                          env->d_scratch_d);
+    int rc;
+    if ((rc = stage_open(env, env->stage[kStageQuery], sp, true))) return rc;
+    rc = with_layout(env->P, [&](auto UA, auto R32) {
+        return launch_lds(env, k_query<UA, R32>, dim3(1), env->lds, env->d_P, what, replica, path, slot, n,
+                          sp[kSpanRow].as<const int32_t>(), sp[kSpanInt].as<int32_t>(), sp[kSpanSvc].as<ongym_service>(),
+                          sp[kSpanReq].as<ongym_request>());
     });
+    return rc ? rc : stage_close(env, sp, true);
 }
 
 int ongym_query_available(ongym_env *env, int32_t replica, int32_t path_id, int32_t *out) {
     if (!env || !out) return ONGYM_E_ARG;
-    int rc = query(env, kQAvailable, replica, path_id, 0, 0);
-    if (rc) return rc;
-    HIP_TRY(env, hipMemcpyAsync(out, env->d_scratch_i, (size_t)env->P.n_slots * 4, hipMemcpyDeviceToHost, env->stream));
-    HIP_TRY(env, hipStreamSynchronize(env->stream));
-    return ONGYM_OK;
+    Span sp[kQuerySpans] = {{}, {out, (size_t)env->P.n_slots * sizeof(int32_t), kOut}};
+    return query(env, kQAvailable, replica, path_id, 0, 0, sp);
 }
 
 int ongym_query_gsnr(ongym_env *env, int32_t replica, int32_t path_id, int32_t slot, int32_t nslots, double out[3]) {
     if (!env || !out) return ONGYM_E_ARG;
-    int rc = query(env, kQGsnr, replica, path_id, slot, nslots);
-    if (rc) return rc;
-    HIP_TRY(env, hipMemcpyAsync(out, env->d_scratch_d, 3 * sizeof(double), hipMemcpyDeviceToHost, env->stream));
-    HIP_TRY(env, hipStreamSynchronize(env->stream));
-    return ONGYM_OK;
+    const int32_t cand[3] = {path_id, slot, nslots};        // calculate_osnr(env, candidate), core/osnr.pyx:21-142
+    return ongym_query_gsnr_many(env, replica, 1, cand, out);
 }
 
 int ongym_query_gsnr_many(ongym_env *env, int32_t replica, int32_t count, const int32_t *cands, double *out) {
@@ -1694,40 +1631,23 @@ int ongym_query_gsnr_many(ongym_env *env, int32_t replica, int32_t count, const 
         if (slot < 0 || n <= 0 || slot + n > env->P.n_slots) return fail_arg(env, "slot range out of the grid");
     }
     HIP_TRY(env, hipSetDevice(env->cfg.device));
-    int32_t *d_c = nullptr;
-    double *d_o = nullptr;
-    HIP_TRY(env, hipMalloc(reinterpret_cast<void **>(&d_c), (size_t)count * 3 * sizeof(int32_t)));
-    if (hipMalloc(reinterpret_cast<void **>(&d_o), (size_t)count * 3 * sizeof(double)) != hipSuccess) {
-        (void)hipFree(d_c);
-        return fail_arg(env, "hipMalloc failed", ONGYM_E_HIP);
-    }
-    hipError_t e = hipMemcpyAsync(d_c, cands, (size_t)count * 3 * sizeof(int32_t), hipMemcpyHostToDevice, env->stream);
-    const int rc = e != hipSuccess ? 0 : with_layout(env->P, [&](auto UA, auto R32) {
-        return launch_lds(env, k_query_gsnr_many<UA, R32>, dim3(count), env->lds, env->d_P, replica, count, d_c, d_o);
+    Span sp[] = {{cands, (size_t)count * 3 * sizeof(int32_t), kIn}, {out, (size_t)count * 3 * sizeof(double), kOut}};
+    int rc;
+    if ((rc = stage_open(env, env->stage[kStageQuery], sp, true))) return rc;
+    rc = with_layout(env->P, [&](auto UA, auto R32) {
+        return launch_lds(env, k_query_gsnr_many<UA, R32>, dim3(count), env->lds, env->d_P, replica, count,
+                          sp[0].as<const int32_t>(), sp[1].as<double>());
     });
-    if (e == hipSuccess && !rc) e = hipMemcpyAsync(out, d_o, (size_t)count * 3 * sizeof(double), hipMemcpyDeviceToHost, env->stream);
-    hipError_t e2 = hipStreamSynchronize(env->stream);
-    (void)hipFree(d_c);
-    (void)hipFree(d_o);
-    if (rc) return rc;
-    if (e != hipSuccess || e2 != hipSuccess) {
-        env->err = std::string("ongym_query_gsnr_many: ") + hipGetErrorString(e != hipSuccess ? e : e2);
-        return ONGYM_E_HIP;
-    }
-    return ONGYM_OK;
+    return rc ? rc : stage_close(env, sp, true);
 }
 
 int ongym_query_candidates(ongym_env *env, const int32_t *row, int32_t total_slots, int32_t nslots,
                            int32_t *starts_out, int32_t *count) {
     if (!env || !row || !starts_out || !count) return ONGYM_E_ARG;
     if (total_slots <= 0 || total_slots > 1023) return fail_arg(env, "total_slots out of range");
-    HIP_TRY(env, hipSetDevice(env->cfg.device));
-    HIP_TRY(env, hipMemcpyAsync(env->d_scratch_i, row, (size_t)total_slots * 4, hipMemcpyHostToDevice, env->stream));
-    int rc = query(env, kQCandidates, 0, total_slots, 0, nslots);
-    if (rc) return rc;
     std::vector<int32_t> flags((size_t)total_slots);
-    HIP_TRY(env, hipMemcpyAsync(flags.data(), env->d_scratch_i + 1024, (size_t)total_slots * 4, hipMemcpyDeviceToHost, env->stream));
-    HIP_TRY(env, hipStreamSynchronize(env->stream));
+    Span sp[kQuerySpans] = {{row, flags.size() * sizeof(int32_t), kIn}, {flags.data(), flags.size() * sizeof(int32_t), kOut}};
+    if (int rc = query(env, kQCandidates, 0, total_slots, 0, nslots, sp)) return rc;
     int32_t k = 0;
     for (int32_t s = 0; s < total_slots; s++) if (flags[s]) starts_out[k++] = s;   // flag -> list, no arithmetic
     *count = k;
@@ -1736,11 +1656,8 @@ int ongym_query_candidates(ongym_env *env, const int32_t *row, int32_t total_slo
 
 int ongym_query_path_free(ongym_env *env, int32_t replica, int32_t path_id, int32_t slot, int32_t nslots, int32_t *out) {
     if (!env || !out) return ONGYM_E_ARG;
-    int rc = query(env, kQPathFree, replica, path_id, slot, nslots);
-    if (rc) return rc;
-    HIP_TRY(env, hipMemcpyAsync(out, env->d_scratch_i, 4, hipMemcpyDeviceToHost, env->stream));
-    HIP_TRY(env, hipStreamSynchronize(env->stream));
-    return ONGYM_OK;
+    Span sp[kQuerySpans] = {{}, {out, sizeof(int32_t), kOut}};
+    return query(env, kQPathFree, replica, path_id, slot, nslots, sp);
 }
 
 int ongym_query_moves(ongym_env *env, int32_t replica, ongym_move *out, int32_t *count) {
@@ -1762,32 +1679,24 @@ int ongym_query_moves(ongym_env *env, int32_t replica, ongym_move *out, int32_t 
 
 int ongym_query_grid(ongym_env *env, int32_t replica, int32_t *out) {
     if (!env || !out) return ONGYM_E_ARG;
-    int rc = query(env, kQGrid, replica, 0, 0, 0);
-    if (rc) return rc;
-    HIP_TRY(env, hipMemcpyAsync(out, env->d_scratch_i, (size_t)env->P.n_links * env->P.n_slots * 4, hipMemcpyDeviceToHost, env->stream));
-    HIP_TRY(env, hipStreamSynchronize(env->stream));
-    return ONGYM_OK;
+    Span sp[kQuerySpans] = {{}, {out, (size_t)env->P.n_links * env->P.n_slots * sizeof(int32_t), kOut}};
+    return query(env, kQGrid, replica, 0, 0, 0, sp);
 }
 
+// Count and records come back in one copy behind one synchronisation: all `capacity` records, of which the first *n reach `out`
 int ongym_query_services(ongym_env *env, int32_t replica, ongym_service *out, int32_t *n) {
     if (!env || !out || !n) return ONGYM_E_ARG;
-    int rc = query(env, kQServices, replica, 0, 0, 0);
-    if (rc) return rc;
-    int32_t head[2];
-    HIP_TRY(env, hipMemcpyAsync(head, env->d_scratch_i, 8, hipMemcpyDeviceToHost, env->stream));
-    HIP_TRY(env, hipStreamSynchronize(env->stream));
-    *n = head[0];
-    if (head[0] > 0) HIP_TRY(env, hipMemcpy(out, env->d_scratch_i + 2, (size_t)head[0] * sizeof(ongym_service), hipMemcpyDeviceToHost));
+    std::vector<ongym_service> recs((size_t)env->P.capacity);
+    Span sp[kQuerySpans] = {{}, {n, sizeof(int32_t), kOut}, {recs.data(), recs.size() * sizeof(ongym_service), kOut}};
+    if (int rc = query(env, kQServices, replica, 0, 0, 0, sp)) return rc;
+    memcpy(out, recs.data(), (size_t)*n * sizeof(ongym_service));
     return ONGYM_OK;
 }
 
 int ongym_query_request(ongym_env *env, int32_t replica, ongym_request *out) {
     if (!env || !out) return ONGYM_E_ARG;
-    int rc = query(env, kQRequest, replica, 0, 0, 0);
-    if (rc) return rc;
-    HIP_TRY(env, hipMemcpyAsync(out, env->d_scratch_i, sizeof(ongym_request), hipMemcpyDeviceToHost, env->stream));
-    HIP_TRY(env, hipStreamSynchronize(env->stream));
-    return ONGYM_OK;
+    Span sp[kQuerySpans] = {{}, {}, {}, {out, sizeof(ongym_request), kOut}};
+    return query(env, kQRequest, replica, 0, 0, 0, sp);
 }
 
 int ongym_stats_get(ongym_env *env, ongym_stats *out) {

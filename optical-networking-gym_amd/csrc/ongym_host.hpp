@@ -10,9 +10,18 @@
 
 using ongym::Params;
 
-// Device staging of one analysis call with host buffers: the call's arrays side by side, grown on demand and never shrunk
+// Device staging of a call with host buffers: the call's arrays side by side, grown on demand and never shrunk (stage_open,
+// ongym_hip.hip).  One slot per family of calls, and no slot shared between calls whose buffers could be in flight together:
 struct Stage { void *base; size_t bytes; };
-enum { kStageBlocks, kStageMetrics, kStageQot, kStageImpact, kStages };   // ongym_observe_blocks, _link_metrics, _service_qot, _action_impact
+enum {
+    kStageBlocks, kStageMetrics, kStageQot, kStageImpact,   // ongym_observe_blocks, _link_metrics, _service_qot, _action_impact
+    kStageStep,     // ongym_step_policy, _step_actions, _step_actions_bundle (B > 256): records | actions | next actions | flags
+    kStagePolicy,   // ongym_policy_actions: actions | flags
+    kStageMask,     // ongym_observe (mask | obs) and ongym_sample_actions (mask | actions): ONE buffer for the action mask
+    kStageReset,    // ongym_reset, _reset_episode_counters: the mask; these two return without synchronising
+    kStageQuery,    // the ongym_query_* calls: used with io_device too (query results are always host buffers)
+    kStages
+};
 
 struct ongym_env {
     ongym_config cfg{};
@@ -26,11 +35,7 @@ struct ongym_env {
     std::vector<void *> allocs;
     std::string err;
     void *d_trace = nullptr;        // owned copy of a host trace
-    ongym_step_rec *d_out = nullptr; size_t d_out_n = 0;
-    int32_t *d_actions = nullptr; int32_t *d_act_out = nullptr; uint8_t *d_flag_out = nullptr; uint8_t *d_mask = nullptr;
-    float *d_obs = nullptr; uint8_t *d_obsmask = nullptr;   // lazily allocated staging for ongym_observe with host buffers
-    Stage stage[kStages] = {};      // one buffer per analysis call, used with host buffers only (stage_open, ongym_hip.hip)
-    int32_t *d_scratch_i = nullptr; size_t scratch_i_bytes = 0; double *d_scratch_d = nullptr;
+    Stage stage[kStages] = {};      // device staging of the calls that take host buffers (stage_open, ongym_hip.hip)
     void *h_pinned = nullptr; size_t h_pinned_bytes = 0;     // pinned staging of ongym_step_actions_bundle
     bool has_source = false;
     uint64_t replica_base = 0;      // global index of this environment's first replica (ongym_seed_base)
