@@ -375,6 +375,51 @@ int ongym_service_qot(ongym_env *env, double *svc_out, double *replica_out, floa
  * times the kernel. */
 int ongym_action_impact(ongym_env *env, int32_t n_actions, const int32_t *actions, const double *svc_in, double *impact_out);
 
+/* What happens when a fibre is cut: per replica and per failed link of a list, the running lightpaths that go down with the
+ * link and how many of them first fit restores through the spectrum that is left, at acceptable QoT (F = n_fail, E = n_links,
+ * C = capacity, K = k_paths, M = n_mods, S = n_slots).  links int32 [batch][F], 1 <= F <= E, link indices in table order;
+ * NULL (only with F = E): column f fails link f.  Every (replica, column) is ONE independent single-link failure on the
+ * replica's current state; duplicates are allowed, an index < 0 or >= E is skipped (status 1).
+ * Scenario (failed link e):
+ *   victims      the running records whose route contains e, in ascending record index (the order of ongym_query_services)
+ *   release      all victims leave at once, each as a departure of the step releases it (_release_path, qrmsa.pyx:1332-1350:
+ *                [slot, slot + n + 1) clamped at S on every link of its route); they interfere with nobody any more
+ *   restoration  one victim after the other in record order.  A victim of format m and n slots is a request of capacity
+ *                n * se[m] (the record keeps no bit rate: "at least the capacity it had"); under format m' it needs
+ *                n' = ceil(n * se[m] / se[m']) slots, a format with n' > S is unusable.  The search is first fit's
+ *                (heuristics.py:923-966) over the routes k = 0..K-1 of the victim's node pair that do not contain e, formats
+ *                m' = M-1 down to 0, the lowest start of _get_candidates(row, n', S) only, the step's GN model over everything
+ *                running in the scenario at that moment (the survivors and the victims restored so far at their new places;
+ *                the replica's launch power; with id tracking, records with the victim's service_id left out, quirk Q12) and
+ *                the step's admission test against minimum_osnr[m'] + the replica's margin.  The first (k, m', a) that passes
+ *                is provisioned as the step provisions ([a, a + n') plus the guard slot unless it ends at S) and joins the
+ *                running set: later victims see its spectrum and its interference.  A victim without one is lost.
+ *   node pair    of a route: the pair with the lowest src * n_nodes + dst whose pair_paths list holds it.  If two pairs that
+ *                hold a route list different routes, the call refuses (ONGYM_E_ARG) rather than guess.
+ * link_out float64 [batch][F][10]:
+ *   0 status              0 evaluated; 1 skipped
+ *   1 victims             count
+ *   2 victim_capacity     sum of n * se[m] over the victims (x channel_width: Gb/s, an upper bound)
+ *   3 restored            count
+ *   4 restored_capacity   sum of n * se[m] (the original's) over the restored
+ *   5 lost_no_spectrum    lost, and no eligible (route, format) had a valid start (no eligible route included)
+ *   6 lost_qot            lost, and at least one start was evaluated and refused
+ *   7 extra_hops          sum over the restored of hops(new route) - hops(old route)
+ *   8 extra_slot_hops     sum over the restored of n' hops(new) - n hops(old)
+ *   9 lowest_margin       min over the restored of GSNR - minimum_osnr[m'] - margin when it was restored (dB); NaN if none
+ *   Status 1: columns 1-9 are NaN.  Column 1 = columns 3 + 5 + 6.
+ * svc_out     NULL, or int32 [batch][F][C] (LARGE: 4 F C bytes per replica, 2.6 GB for 65 536 replicas of NSFNET at C = 448 and
+ *             F = E = 22; ask for it on small batches or short link lists): per record -1 if it is no victim (or at and beyond the
+ *             running count), the reject action K M S if it is lost, else the action index k M S + (M-1-m') S + a of its
+ *             restoration.
+ * Refused (ONGYM_E_ARG): F out of range, NULL links with F != E, NULL link_out, n_mods_consider < n_mods (no format window, as
+ * ongym_observe_blocks).
+ * Read-only: no replica state, statistic, counter (total_gn_evals included), disrupted flag, move log or random-number
+ * position changes.  Buffers: host buffers (staged through a device buffer grown on demand; the call synchronises), or device
+ * buffers with cfg.io_device (then the call only launches on the environment's stream and nothing synchronises).
+ * ongym_last_kernel_ms times the kernel. */
+int ongym_failure_impact(ongym_env *env, int32_t n_fail, const int32_t *links, double *link_out, int32_t *svc_out);
+
 /* One uniformly random VALID action per replica from an action mask [batch][k_paths*Mc*n_slots + 1] (as ongym_observe
  * writes it): what gymnasium's `action_space.sample(mask=info["mask"])` does on the reference's Discrete action space
  * (qrmsa.pyx:319-321; wrappers/qrmsa_gym.py:74-75 hands the mask out) - the masked random policy that exercises the

@@ -2,6 +2,7 @@
 // Build: hipcc --offload-arch=gfx950 -O3 -fPIC -shared -o libongym_hip.so ongym_hip.hip   (see __graft_entry__.build)
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -26,6 +27,7 @@
 #include "ongym_metrics.hpp"       // per-link fragmentation metrics and link statistics (ongym_link_metrics)
 #include "ongym_qot.hpp"           // current QoT of every running lightpath (ongym_service_qot)
 #include "ongym_impact.hpp"        // effect of candidate actions on the running lightpaths (ongym_action_impact)
+#include "ongym_failure.hpp"       // single-link failures and first-fit restoration (ongym_failure_impact)
 
 using namespace ongym;
 
@@ -700,6 +702,23 @@ static int build(ongym_env *env, const ongym_config *c) {
     }
     if ((rc = upload(env, nreq_tab.data(), nreq_tab.size(), &P.nreq_tab))) return rc;
     if ((rc = upload(env, c->pair_paths, (size_t)N * N * K, &P.pair_paths))) return rc;
+    {   // route -> node pair for ongym_failure_impact.  Both directions of a pair share their routes in the same order
+        // (topology.pyx:310-355): every pair that lists a route must list the same K routes, or the call refuses
+        std::vector<int32_t> pp((size_t)NP, -1);
+        for (int pr = 0; pr < N * N && env->path_pair_err.empty(); pr++)
+            for (int k = 0; k < K; k++) {
+                const int p = c->pair_paths[(size_t)pr * K + k];
+                if (p < 0) continue;
+                if (pp[p] < 0) pp[p] = pr;
+                else if (pp[p] != pr && !std::equal(c->pair_paths + (size_t)pr * K, c->pair_paths + (size_t)(pr + 1) * K,
+                                                    c->pair_paths + (size_t)pp[p] * K)) {
+                    env->path_pair_err = "route " + std::to_string(p) + " is listed by node pairs " + std::to_string(pp[p]) + " and " +
+                                         std::to_string(pr) + " with different route lists: no node pair for failure impact";
+                    break;
+                }
+            }
+        if ((rc = upload(env, pp.data(), pp.size(), &env->d_path_pair))) return rc;
+    }
     if ((rc = upload(env, c->path_hops, (size_t)NP, &P.path_hops))) return rc;
     if ((rc = upload(env, c->path_links, (size_t)NP * H, &P.path_links))) return rc;
     if ((rc = upload(env, mask.data(), mask.size(), &P.path_mask))) return rc;
@@ -1443,6 +1462,32 @@ int ongym_action_impact(ongym_env *env, int32_t n_actions, const int32_t *action
         return with_layout(P, [&](auto UA, auto R32) {     // attenuation and the stored record codec
             return launch_lds(env, k_action_impact<UA, R32>, dim3(P.batch), lds, env->d_P, (int)n_actions,
                               sp[2].as<const int32_t>(), sp[1].as<const double>(), sp[0].as<double>());
+        });
+    });
+    return rc ? rc : stage_close(env, sp);
+}
+
+int ongym_failure_impact(ongym_env *env, int32_t n_fail, const int32_t *links, double *link_out, int32_t *svc_out) {
+    if (!env) return ONGYM_E_ARG;
+    if (!link_out) return fail_arg(env, "null link_out");
+    const Params &P = env->P;
+    if (n_fail < 1 || n_fail > P.n_links) return fail_arg(env, "n_fail must lie in [1, n_links]");
+    if (!links && n_fail != P.n_links) return fail_arg(env, "null links: n_fail must be n_links");
+    if (P.n_mods_consider < P.n_mods)
+        return fail_arg(env, "restoration searches every format: it needs modulations_to_consider == n_mods");
+    if (!env->path_pair_err.empty()) return fail_arg(env, env->path_pair_err.c_str());
+    const size_t lds = failure_lds_bytes(P);
+    if (lds > 160 * 1024) return fail_arg(env, "the failure kernel's LDS block exceeds 160 KiB: lower capacity", ONGYM_E_LIMIT);
+    HIP_TRY(env, hipSetDevice(env->cfg.device));
+    const size_t B = (size_t)P.batch, F = (size_t)n_fail;
+    Span sp[] = {{link_out, B * F * kFailureImpact * sizeof(double), kOut},                        // staging: link_out | svc_out | links
+                 {svc_out, B * F * P.capacity * sizeof(int32_t), kOut}, {links, B * F * sizeof(int32_t), kIn}};
+    int rc;
+    if ((rc = stage_open(env, env->stage[kStageFailure], sp))) return rc;
+    rc = timed_launch(env, [&] {
+        return with_layout(P, [&](auto UA, auto R32) {     // attenuation and the stored record codec
+            return launch_lds(env, k_failure_impact<UA, R32>, dim3(P.batch, n_fail), lds, env->d_P, (int)n_fail,
+                              sp[2].as<const int32_t>(), env->d_path_pair, sp[0].as<double>(), sp[1].as<int32_t>());
         });
     });
     return rc ? rc : stage_close(env, sp);

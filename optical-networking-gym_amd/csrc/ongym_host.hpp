@@ -15,6 +15,7 @@ using ongym::Params;
 struct Stage { void *base; size_t bytes; };
 enum {
     kStageBlocks, kStageMetrics, kStageQot, kStageImpact,   // ongym_observe_blocks, _link_metrics, _service_qot, _action_impact
+    kStageFailure,  // ongym_failure_impact: link_out | svc_out | links
     kStageStep,     // ongym_step_policy, _step_actions, _step_actions_bundle (B > 256): records | actions | next actions | flags
     kStagePolicy,   // ongym_policy_actions: actions | flags
     kStageMask,     // ongym_observe (mask | obs) and ongym_sample_actions (mask | actions): ONE buffer for the action mask
@@ -52,6 +53,10 @@ struct ongym_env {
     void *state_alt[9] = {};        // ongym_fork: the second set of state arrays (lazily allocated; swapped with Params' set)
     int32_t *d_state_idx = nullptr; // [batch] replica list of a save / load, or a host fork list
     void *d_state_stage = nullptr; size_t state_stage_bytes = 0;   // device copy of a host blob
+    // ongym_failure_impact (ongym_failure.hpp): route -> node pair (the lowest src * n_nodes + dst whose pair_paths list holds
+    // it; -1: in no list), built at create; a message instead when two pairs disagree about a route's list
+    const int32_t *d_path_pair = nullptr;
+    std::string path_pair_err;
 };
 
 #define HIP_TRY(env, expr)                                                                               \

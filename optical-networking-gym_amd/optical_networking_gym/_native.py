@@ -38,6 +38,8 @@ LINK_QOT = ("lightpaths", "lowest_margin", "below_minimum")  # ... and link_out 
 ACTION_IMPACT = ("status", "affected", "below_minimum_after", "newly_below_minimum", "newly_below_margin", "lowest_margin_after",
                  "largest_drop", "lowest_margin_record")     # ongym_action_impact: impact_out entries per (replica, action)
 MAX_IMPACT_ACTIONS = 256                                    # ... and the longest action list per replica
+FAILURE_IMPACT = ("status", "victims", "victim_capacity", "restored", "restored_capacity", "lost_no_spectrum", "lost_qot",
+                  "extra_hops", "extra_slot_hops", "lowest_margin")   # ongym_failure_impact: link_out entries per (replica, link)
 
 _i32p, _f64p = C.POINTER(C.c_int32), C.POINTER(C.c_double)
 
@@ -229,6 +231,9 @@ def _declare(lib):
     if hasattr(lib, "ongym_action_impact"):     # (tools/time_action_impact.py --fork-loop times an older build through ONGYM_HIP_LIB)
         lib.ongym_action_impact.argtypes = [vp, C.c_int32, vp, vp, vp]
         lib.ongym_action_impact.restype = C.c_int32
+    if hasattr(lib, "ongym_failure_impact"):    # (an older build named by ONGYM_HIP_LIB has none)
+        lib.ongym_failure_impact.argtypes = [vp, C.c_int32, vp, vp, vp]
+        lib.ongym_failure_impact.restype = C.c_int32
     if hasattr(lib, "ongym_sample_actions"):
         lib.ongym_sample_actions.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp]
         lib.ongym_sample_actions.restype = C.c_int32
@@ -291,7 +296,7 @@ def _declare_tail(lib, vp, skip=()):
 
 EXPORTED_SYMBOLS = (
     "ongym_create", "ongym_destroy", "ongym_seed", "ongym_seed_base", "ongym_set_requests", "ongym_reset", "ongym_reset_episode_counters", "ongym_step_policy",
-    "ongym_step_actions", "ongym_step_actions_bundle", "ongym_policy_actions", "ongym_observe", "ongym_observe_blocks", "ongym_link_metrics", "ongym_service_qot", "ongym_action_impact", "ongym_sample_actions", "ongym_masked_categorical", "ongym_masked_categorical_backward",
+    "ongym_step_actions", "ongym_step_actions_bundle", "ongym_policy_actions", "ongym_observe", "ongym_observe_blocks", "ongym_link_metrics", "ongym_service_qot", "ongym_action_impact", "ongym_failure_impact", "ongym_sample_actions", "ongym_masked_categorical", "ongym_masked_categorical_backward",
     "ongym_masked_categorical_rows", "ongym_masked_categorical_backward_rows", "ongym_gae", "ongym_state_size", "ongym_state_save", "ongym_state_load", "ongym_fork", "ongym_query_available", "ongym_query_gsnr", "ongym_query_gsnr_many", "ongym_query_moves", "ongym_query_grid",
     "ongym_query_services", "ongym_query_request", "ongym_query_candidates", "ongym_query_path_free",
     "ongym_stats_get", "ongym_sync", "ongym_set_stream", "ongym_last_kernel_ms", "ongym_query_occupancy", "ongym_query_occupancy_policy",

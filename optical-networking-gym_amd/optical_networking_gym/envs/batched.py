@@ -378,6 +378,72 @@ class BatchedQRMSAEnv:
                                                  res.ctypes.data), "ongym_action_impact")
         return res
 
+    # ---- single-link failures and first-fit restoration (ongym_failure_impact, include/ongym.h) ----------------------------
+    def failure_impact(self, links=None, out=None, detail=False):
+        """What happens when a fibre is cut: float64 [B, F, 10], columns nat.FAILURE_IMPACT (status, victims, their capacity,
+        restored, restored capacity, lost for want of spectrum, lost on QoT, extra hops, extra slot-hops, lowest margin of a
+        restoration), one independent single-link failure per (replica, column) with first-fit restoration of the victims in
+        record order.  links: int32 [B, F] (or [B]: F = 1) of link indices in table order, 1 <= F <= n_links; None: every link,
+        F = n_links.  detail=True also returns int32 [B, F, C]: per record -1 (no victim), the reject action (lost) or the
+        action index of its restoration - 4 F C bytes per replica, for small batches.  Read-only.  A host environment takes and
+        returns numpy arrays.  An io_device environment takes torch tensors on its device and writes into `out` (the link
+        tensor, or with detail the pair (link, svc)), on torch's current stream (env.set_stream), without synchronising."""
+        c = self.holder.struct
+        B, E = self.batch_size, c.n_links
+        if c.n_mods_consider < c.n_mods:
+            raise ValueError("failure_impact searches every format: it needs modulations_to_consider == the number of modulations")
+        ncol = len(nat.FAILURE_IMPACT)
+        if c.io_device:
+            import torch
+            from .. import rl
+            dev = rl._device(self)
+            F = E
+            if links is not None:
+                if not isinstance(links, torch.Tensor) or links.dtype != torch.int32 or links.device != dev:
+                    raise ValueError(f"links must be a torch.int32 tensor on {dev}")
+                if links.dim() == 1:
+                    links = links.reshape(-1, 1)
+                if links.dim() != 2 or links.shape[0] != B or not links.is_contiguous():
+                    raise ValueError(f"links must be contiguous with shape ({B}, F) or ({B},)")
+                F = int(links.shape[1])
+                if links.data_ptr() % 4:
+                    raise ValueError("links must be aligned to its element size")
+            if not 1 <= F <= E:
+                raise ValueError(f"the number of failed links per replica must lie in [1, {E}]")
+            if out is None:
+                raise ValueError("an io_device environment needs out, a float64 tensor of shape (B, F, 10) (detail: with an int32 "
+                                 "tensor of shape (B, F, C), as a pair)")
+            if detail and (not isinstance(out, (tuple, list)) or len(out) != 2):
+                raise ValueError("with detail, out must be the pair (link, svc)")
+            link_t, svc_t = out if detail else (out, None)
+            self._check_tensor(link_t, "out" if not detail else "out[0]", torch.float64, (B, F, ncol), dev)
+            if detail:
+                self._check_tensor(svc_t, "out[1]", torch.int32, (B, F, c.capacity), dev)
+            rl._check_stream(self)
+            self._check(self.lib.ongym_failure_impact(self._h, F, C.c_void_p(links.data_ptr() if links is not None else None),
+                                                      C.c_void_p(link_t.data_ptr()),
+                                                      C.c_void_p(svc_t.data_ptr() if detail else None)), "ongym_failure_impact")
+            return out
+        if out is not None:
+            raise ValueError("out is for io_device environments; a host environment returns new arrays")
+        F = E
+        if links is not None:
+            if not isinstance(links, np.ndarray) or links.dtype != np.int32:
+                raise ValueError("links must be a numpy int32 array")
+            if links.ndim == 1:
+                links = links.reshape(-1, 1)
+            if links.ndim != 2 or links.shape[0] != B:
+                raise ValueError(f"links must have shape ({B}, F) or ({B},)")
+            F = int(links.shape[1])
+            links = np.ascontiguousarray(links)
+        if not 1 <= F <= E:
+            raise ValueError(f"the number of failed links per replica must lie in [1, {E}]")
+        res = np.zeros((B, F, ncol), np.float64)
+        svc = np.zeros((B, F, c.capacity), np.int32) if detail else None
+        self._check(self.lib.ongym_failure_impact(self._h, F, links.ctypes.data if links is not None else None, res.ctypes.data,
+                                                  svc.ctypes.data if detail else None), "ongym_failure_impact")
+        return (res, svc) if detail else res
+
     # ---- queries (plugin API) ----------------------------------------------------------------------------------------
     def available_slots(self, replica: int, path_id: int) -> np.ndarray:
         out = np.zeros(self.holder.struct.n_slots, np.int32)

@@ -579,6 +579,25 @@ class QRMSAEnv:
         whole = ("status", "affected", "below_minimum_after", "newly_below_minimum", "newly_below_margin", "lowest_margin_record")
         return {k: (int(v) if k in whole and not np.isnan(v) else float(v)) for k, v in zip(nat.ACTION_IMPACT, row)}
 
+    def failure_impact(self, link) -> dict:
+        """What a cut of `link` (its index, or a (u, v) node pair of the topology) would do now, with first-fit restoration of
+        the lightpaths that cross it (BatchedQRMSAEnv.failure_impact): a dict with the keys of nat.FAILURE_IMPACT (the counts,
+        the capacities and the hop sums are ints where they are defined), plus `restorations`, a list of (service record index,
+        route index, modulation index, initial_slot), and `lost`, the record indices of the victims that found no place."""
+        if isinstance(link, (tuple, list)):
+            u, v = link
+            link = self.topology[u][v]["index"]
+        row, svc = self._dev.failure_impact(np.array([[int(link)]], np.int32), detail=True)
+        c = self._dev.holder.struct
+        M, S = c.n_mods, c.n_slots
+        out = {k: (float(v) if k == "lowest_margin" or np.isnan(v) else int(v)) for k, v in zip(nat.FAILURE_IMPACT, row[0, 0])}
+        reject = c.k_paths * M * S
+        hit = np.flatnonzero(svc[0, 0] >= 0)
+        out["restorations"] = [(int(i), int(a) // (M * S), M - 1 - (int(a) // S) % M, int(a) % S)
+                               for i, a in zip(hit, svc[0, 0, hit]) if a != reject]
+        out["lost"] = [int(i) for i in hit if svc[0, 0, i] == reject]
+        return out
+
     def close(self):
         if self.file_stats is not None:
             self.file_stats.close()
