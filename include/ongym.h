@@ -420,6 +420,62 @@ int ongym_action_impact(ongym_env *env, int32_t n_actions, const int32_t *action
  * ongym_last_kernel_ms times the kernel. */
 int ongym_failure_impact(ongym_env *env, int32_t n_fail, const int32_t *links, double *link_out, int32_t *svc_out);
 
+/* What the network could still carry right now: per replica and per candidate action of a list, first fit's admission decision
+ * for EVERY request the traffic model can draw - every unordered node pair and every bit rate of a list - on the replica's
+ * current state (N = n_nodes, K = k_paths, M = n_mods, S = n_slots, C = capacity, Q = N (N - 1) / 2, A = n_actions, R = n_rates).
+ * Cells      node pairs are the unordered pairs s < d in lexicographic order, q = 0..Q-1; the routes of pair q are
+ *            pair_paths[(s N + d) K + k].  Both directions of a pair must list the same routes (checked at create: the create
+ *            succeeds, this call refuses with ONGYM_E_ARG and names the pair).  rates float [R], 1 <= R <= 16, Gb/s, shared by
+ *            all replicas, ALWAYS a host array (it travels with the launch, also with cfg.io_device); NULL with
+ *            n_rates == n_bit_rates: the configuration's discrete bit rates (refused in continuous mode or with another
+ *            n_rates).  Rate r needs (int)ceil((double)r / (mod_se[m] * nslots_width)) slots under format m, the step's own
+ *            expression (for the configured rates: nreq_tab); a format with n < 1 or n > S is unusable.
+ * Scenarios  actions int32 [batch][A], 1 <= A <= 256; NULL (only with A = 1): the state as it is.  Every (replica, a) is ONE
+ *            independent scenario on the replica's current state; the action is decoded for the replica's current request as
+ *            ongym_action_impact decodes it.  Status:
+ *   0  the action decodes and its slots are free: the candidate is provisioned as the step provisions ([a, a + n) plus the
+ *      guard slot unless it ends at S) and appended as a running record at `active` (with id tracking: with the current
+ *      request's id); then the map is taken.  As in ongym_action_impact the candidate's own QoT is not evaluated.
+ *   1  NULL, an index < 0, the reject action or beyond it, or no current request: nothing is applied, the row is the map of the
+ *      state as it is (one call yields the baseline and the candidates)
+ *   2  spectrum not free, or no such route / format / slot count (ongym_action_impact's status 2): summary columns 1-7 NaN, map
+ *      entries -1, margins NaN
+ *   3  the running count is already C: as status 2 (a candidate that is also not free has status 2)
+ * A cell (q, r) of a scenario is first fit's decision (heuristics.py:923-966) for a request of rate r between the pair: routes
+ * k = 0..K-1 (stop at -1), formats M-1 down to 0, only the lowest start of _get_candidates(row, n, S), the step's GN model over
+ * everything running in the scenario at the replica's launch power, the step's admission test against minimum_osnr[m] + the
+ * replica's margin, the exact ASE lower bound where first fit uses it.  A probe has no service id: nobody is left out of its
+ * interferers (quirk Q12 concerns requests that carry an id).  No probe is provisioned: cells do not see each other.  Outcome:
+ * admitted with (k, m, a); blocked for spectrum (no (route, format) had a valid start); blocked on QoT (at least one start was
+ * evaluated, by bound or GN sum, and refused: the rule of lost_qot in ongym_failure_impact).
+ * summary_out float64 [batch][A][8]:
+ *   0 status
+ *   1 admitted              cells
+ *   2 blocked_no_spectrum   cells
+ *   3 blocked_qot           cells                                  (columns 1 + 2 + 3 = Q R)
+ *   4 blocking_probability  sum of w[q][r] over the blocked cells
+ *   5 bit_rate_blocking     sum of w rate over the blocked cells / sum of w rate over all cells
+ *   6 lowest_margin         min over the admitted cells of GSNR - minimum_osnr[m] - margin (dB); NaN if none is admitted
+ *   7 detoured              admitted cells with k > 0
+ * weights     float64 [Q][R], or NULL: uniform 1 / (Q R).  The sums run in a fixed order, pair-major, without floating-point
+ *             atomics: the same state and inputs give the same bytes on every call.
+ * map_out     NULL, or int32 [batch][A][Q][R] (LARGE: 4 A Q R bytes per replica, 3.9 GB for 65 536 replicas of NSFNET with four
+ *             rates and A = 41; ask for it on small batches or short action lists): k M S + (M-1-m) S + a of an admitted cell,
+ *             K M S blocked for spectrum, K M S + 1 blocked on QoT.
+ * margin_out  NULL, or float32 [batch][A][Q][R]: the admitted cell's margin (column 6's quantity), NaN otherwise.
+ * Refused (ONGYM_E_ARG): A or R out of range, NULL actions with A != 1, NULL summary_out, a non-finite or non-positive rate,
+ * n_mods_consider < n_mods (no format window, as ongym_observe_blocks), asymmetric pair lists.
+ * Read-only: no replica state, statistic, counter (total_gn_evals included), disrupted flag, move log or random-number
+ * position changes.  Buffers (all but rates): host buffers (staged through a device buffer grown on demand; the call
+ * synchronises), or device buffers with cfg.io_device (then the call only launches on the environment's stream and nothing
+ * synchronises).  ongym_last_kernel_ms times the kernel(s).
+ * Launch geometry: small batches split a scenario's pairs over several wavefronts and add their partial sums in a fixed order
+ * (a buffer for them is allocated at create; the call itself never allocates).  ONGYM_ADMISSION_GROUPS=<g> in the environment at
+ * create forces g wavefronts per scenario: a measurement and test knob, not for production (the split changes the order of the
+ * sums of columns 4 and 5, i.e. their last bits, and nothing else). */
+int ongym_admission_map(ongym_env *env, int32_t n_actions, const int32_t *actions, int32_t n_rates, const float *rates,
+                        const double *weights, double *summary_out, int32_t *map_out, float *margin_out);
+
 /* One uniformly random VALID action per replica from an action mask [batch][k_paths*Mc*n_slots + 1] (as ongym_observe
  * writes it): what gymnasium's `action_space.sample(mask=info["mask"])` does on the reference's Discrete action space
  * (qrmsa.pyx:319-321; wrappers/qrmsa_gym.py:74-75 hands the mask out) - the masked random policy that exercises the

@@ -28,6 +28,7 @@
 #include "ongym_qot.hpp"           // current QoT of every running lightpath (ongym_service_qot)
 #include "ongym_impact.hpp"        // effect of candidate actions on the running lightpaths (ongym_action_impact)
 #include "ongym_failure.hpp"       // single-link failures and first-fit restoration (ongym_failure_impact)
+#include "ongym_admission.hpp"     // first-fit admission of every node pair and bit rate (ongym_admission_map)
 
 using namespace ongym;
 
@@ -529,6 +530,28 @@ static int stage_close(ongym_env *env, const Span (&sp)[N], bool always = false)
     return ONGYM_OK;
 }
 
+// Wavefronts per scenario of k_admission_map: the pairs are split into 2, 4, 8 or 16 groups until scenarios x
+// groups reach kAdmissionFill wavefronts.  Measured on NSFNET-320 (profiles/r16_admission_map.txt): 16 384 scenarios run 6 to 8 %
+// faster with 8 groups than with one, from 65 536 scenarios up the groups make no difference beyond the noise of 1.5 %.
+// The groups' partial sums lie in a buffer allocated at create (admission_part_rows): a call never allocates.  A split therefore
+// has scenarios x groups < 2 kAdmissionFill rows, and so has one forced with ONGYM_ADMISSION_GROUPS (read at create).
+constexpr size_t kAdmissionFill = 131072;
+static size_t admission_part_rows(const Params &P) {
+    return std::min<size_t>(2 * kAdmissionFill, (size_t)P.batch * kMaxAdmissionActions * 16);
+}
+
+// At the end of create, after every allocation of build(): the buffer of the groups' partial sums (so that no call allocates, and
+// the state arrays lie where they lay without it), and the measurement knob
+static int admission_prepare(ongym_env *env) {
+    Stage &st = env->stage[kStageAdmissionPart];
+    const size_t bytes = admission_part_rows(env->P) * kAdmissionPart * sizeof(double);
+    HIP_TRY(env, hipMalloc(&st.base, bytes));
+    st.bytes = bytes;
+    const char *g = std::getenv("ONGYM_ADMISSION_GROUPS");
+    env->admission_groups = g ? std::max(0, std::atoi(g)) : 0;
+    return 0;
+}
+
 static int build(ongym_env *env, const ongym_config *c) {
     Params &P = env->P;
     if (c->n_nodes <= 1 || c->n_links <= 0 || c->n_paths <= 0 || c->k_paths <= 0 || c->max_hops <= 0 ||
@@ -719,6 +742,15 @@ static int build(ongym_env *env, const ongym_config *c) {
             }
         if ((rc = upload(env, pp.data(), pp.size(), &env->d_path_pair))) return rc;
     }
+    // ongym_admission_map walks the unordered node pairs: both directions of a pair must list the same routes in the same order
+    for (int s = 0; s < N && env->admission_pair_err.empty(); s++)
+        for (int d = s + 1; d < N; d++)
+            if (!std::equal(c->pair_paths + ((size_t)s * N + d) * K, c->pair_paths + ((size_t)s * N + d + 1) * K,
+                            c->pair_paths + ((size_t)d * N + s) * K)) {
+                env->admission_pair_err = "node pair (" + std::to_string(s) + ", " + std::to_string(d) +
+                                          ") lists different routes in its two directions: no unordered pair for the admission map";
+                break;
+            }
     if ((rc = upload(env, c->path_hops, (size_t)NP, &P.path_hops))) return rc;
     if ((rc = upload(env, c->path_links, (size_t)NP * H, &P.path_links))) return rc;
     if ((rc = upload(env, mask.data(), mask.size(), &P.path_mask))) return rc;
@@ -1089,6 +1121,7 @@ int ongym_create(const ongym_config *cfg, ongym_env **out) {
         env->stream = env->own_stream;
         if (hipEventCreate(&env->ev0) != hipSuccess || hipEventCreate(&env->ev1) != hipSuccess) { env->err = "hipEventCreate failed"; rc = ONGYM_E_HIP; break; }
         rc = build(env, cfg);
+        if (!rc) rc = admission_prepare(env);
     } while (0);
     if (rc) {
         g_create_error = env->err;
@@ -1489,6 +1522,60 @@ int ongym_failure_impact(ongym_env *env, int32_t n_fail, const int32_t *links, d
             return launch_lds(env, k_failure_impact<UA, R32>, dim3(P.batch, n_fail), lds, env->d_P, (int)n_fail,
                               sp[2].as<const int32_t>(), env->d_path_pair, sp[0].as<double>(), sp[1].as<int32_t>());
         });
+    });
+    return rc ? rc : stage_close(env, sp);
+}
+
+static int admission_groups(const ongym_env *env, size_t scenarios, int Q) {
+    size_t g = 1;
+    if (env->admission_groups > 0) g = (size_t)env->admission_groups;
+    else while (g < 16 && scenarios * g < kAdmissionFill) g *= 2;
+    g = std::min<size_t>(std::min<size_t>(g, 64), (size_t)Q);
+    return (int)std::max<size_t>(1, std::min(g, admission_part_rows(env->P) / scenarios));
+}
+
+int ongym_admission_map(ongym_env *env, int32_t n_actions, const int32_t *actions, int32_t n_rates, const float *rates,
+                        const double *weights, double *summary_out, int32_t *map_out, float *margin_out) {
+    if (!env) return ONGYM_E_ARG;
+    if (!summary_out) return fail_arg(env, "null summary_out");
+    const Params &P = env->P;
+    if (n_actions < 1 || n_actions > kMaxAdmissionActions) return fail_arg(env, "n_actions must lie in [1, 256]");
+    if (!actions && n_actions != 1) return fail_arg(env, "null actions: n_actions must be 1");
+    if (n_rates < 1 || n_rates > kMaxAdmissionRates) return fail_arg(env, "n_rates must lie in [1, 16]");
+    AdmissionRates rv{};
+    if (!rates) {
+        if (P.bit_rate_mode != 0 || n_rates != P.n_bit_rates || (int)env->cfg_bit_rates.size() != n_rates)
+            return fail_arg(env, "null rates: discrete bit rates and n_rates == n_bit_rates");
+        for (int r = 0; r < n_rates; r++) rv.v[r] = (float)env->cfg_bit_rates[r];
+    } else
+        for (int r = 0; r < n_rates; r++) rv.v[r] = rates[r];
+    for (int r = 0; r < n_rates; r++)
+        if (!std::isfinite(rv.v[r]) || !(rv.v[r] > 0.0f)) return fail_arg(env, "every rate must be finite and positive");
+    if (P.n_mods_consider < P.n_mods)
+        return fail_arg(env, "the admission map searches every format: it needs modulations_to_consider == n_mods");
+    if (!env->admission_pair_err.empty()) return fail_arg(env, env->admission_pair_err.c_str());
+    const size_t lds = lds_bytes(P);
+    if (lds > 160 * 1024) return fail_arg(env, "the admission kernel's LDS block exceeds 160 KiB: lower capacity", ONGYM_E_LIMIT);
+    HIP_TRY(env, hipSetDevice(env->cfg.device));
+    const size_t B = (size_t)P.batch, A = (size_t)n_actions, R = (size_t)n_rates, Q = (size_t)P.n_nodes * (P.n_nodes - 1) / 2;
+    const int groups = admission_groups(env, B * A, (int)Q);
+    Span sp[] = {{summary_out, B * A * kAdmissionMap * sizeof(double), kOut},          // staging: summary | map | margin | weights | actions
+                 {map_out, B * A * Q * R * sizeof(int32_t), kOut}, {margin_out, B * A * Q * R * sizeof(float), kOut},
+                 {weights, Q * R * sizeof(double), kIn}, {actions, B * A * sizeof(int32_t), kIn}};
+    int rc;
+    if ((rc = stage_open(env, env->stage[kStageAdmission], sp))) return rc;
+    double *part = groups > 1 ? static_cast<double *>(env->stage[kStageAdmissionPart].base) : nullptr;   // allocated at create
+    rc = timed_launch(env, [&]() -> int {
+        const int lrc = with_layout(P, [&](auto UA, auto R32) {     // attenuation and the stored record codec
+            return launch_lds(env, k_admission_map<UA, R32>, dim3(P.batch, n_actions, groups), lds, env->d_P, (int)n_actions,
+                              sp[4].as<const int32_t>(), (int)n_rates, rv, sp[3].as<const double>(), groups, sp[0].as<double>(),
+                              part, sp[1].as<int32_t>(), sp[2].as<float>());
+        });
+        if (lrc || groups == 1) return lrc;
+        hipLaunchKernelGGL(k_admission_reduce, dim3((unsigned)((B * A + 255) / 256)), dim3(256), 0, env->stream, B * A, groups,
+                           (const double *)part, sp[0].as<double>());
+        HIP_TRY(env, hipGetLastError());
+        return 0;
     });
     return rc ? rc : stage_close(env, sp);
 }

@@ -16,6 +16,8 @@ struct Stage { void *base; size_t bytes; };
 enum {
     kStageBlocks, kStageMetrics, kStageQot, kStageImpact,   // ongym_observe_blocks, _link_metrics, _service_qot, _action_impact
     kStageFailure,  // ongym_failure_impact: link_out | svc_out | links
+    kStageAdmission,      // ongym_admission_map: summary | map | margin | weights | actions
+    kStageAdmissionPart,  // ... and its groups' partial sums (device only, allocated at create and never grown)
     kStageStep,     // ongym_step_policy, _step_actions, _step_actions_bundle (B > 256): records | actions | next actions | flags
     kStagePolicy,   // ongym_policy_actions: actions | flags
     kStageMask,     // ongym_observe (mask | obs) and ongym_sample_actions (mask | actions): ONE buffer for the action mask
@@ -57,6 +59,9 @@ struct ongym_env {
     // it; -1: in no list), built at create; a message instead when two pairs disagree about a route's list
     const int32_t *d_path_pair = nullptr;
     std::string path_pair_err;
+    // ongym_admission_map (ongym_admission.hpp): a message when a node pair lists different routes in its two directions
+    std::string admission_pair_err;
+    int admission_groups = 0;       // ONGYM_ADMISSION_GROUPS at create: wavefront groups per scenario instead of the rule's (0: the rule)
 };
 
 #define HIP_TRY(env, expr)                                                                               \

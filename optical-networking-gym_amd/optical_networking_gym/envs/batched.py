@@ -444,6 +444,131 @@ class BatchedQRMSAEnv:
                                                   svc.ctypes.data if detail else None), "ongym_failure_impact")
         return (res, svc) if detail else res
 
+    # ---- first-fit admission of every node pair and bit rate (ongym_admission_map, include/ongym.h) ------------------------
+    @property
+    def admission_pairs(self) -> np.ndarray:
+        """int32 [Q, 2]: the unordered node pairs (s, d), s < d, in the order of admission_map's cells"""
+        N = self.holder.struct.n_nodes
+        return np.array([(s, d) for s in range(N) for d in range(s + 1, N)], np.int32).reshape(-1, 2)
+
+    def admission_weights(self) -> np.ndarray:
+        """float64 [Q, R]: the probability that the next request is for (pair q, configured bit rate r).  The pair's is
+        p_s p_d / (1 - p_s) + p_d p_s / (1 - p_d), the two orders of the two-stage draw (source by node probability, destination
+        among the others; qrmsa.pyx:1134-1148), from the differences of node_cum; the rate's from those of bit_rate_cum."""
+        if self.holder.struct.bit_rate_mode != 0:
+            raise ValueError("traffic weights need discrete bit rates")
+        p = np.diff(self.holder._keep["node_cum"], prepend=0.0)
+        p = p / p.sum()
+        pr = np.diff(self.holder._keep["bit_rate_cum"], prepend=0.0)
+        pr = pr / pr.sum()
+        pair = np.array([p[s] * p[d] / (1.0 - p[s]) + p[d] * p[s] / (1.0 - p[d]) for s, d in self.admission_pairs])
+        return np.ascontiguousarray(pair[:, None] * pr[None, :])
+
+    def admission_map(self, actions=None, rates=None, weights="traffic", out=None, detail=False):
+        """What the network could still carry: float64 [B, A, 8], columns nat.ADMISSION_MAP (status, admitted cells, blocked for
+        want of spectrum, blocked on QoT, blocking probability, bit-rate blocking, lowest margin of an admitted cell, admitted on
+        a route k > 0), first fit's admission decision for every cell (node pair q of admission_pairs, bit rate r) on the
+        replica's state after each candidate action.  actions: int32 [B, A] (or [B]: A = 1) of full step action indices for the
+        current request, 1 <= A <= nat.MAX_IMPACT_ACTIONS; None: the state as it is (A = 1).  rates: up to
+        nat.MAX_ADMISSION_RATES bit rates in Gb/s (any sequence, always on the host); None: the configured discrete rates.
+        weights: float64 [Q, R]; "traffic": the configuration's request probabilities (admission_weights; only with rates=None);
+        None: uniform.  detail=True also returns the map int32 [B, A, Q, R] (k M S + (M-1-m) S + a admitted, K M S blocked for
+        spectrum, K M S + 1 blocked on QoT, -1 status >= 2) and the margins float32 [B, A, Q, R] - 8 A Q R bytes per replica, for
+        small batches.  Read-only.  A host environment takes and returns numpy arrays.  An io_device environment takes torch
+        tensors on its device (actions, weights) and writes into `out` (the summary tensor, or with detail the triple (summary,
+        map, margin)), on torch's current stream (env.set_stream), without synchronising."""
+        c = self.holder.struct
+        B, N = self.batch_size, c.n_nodes
+        Q = N * (N - 1) // 2
+        if c.n_mods_consider < c.n_mods:
+            raise ValueError("admission_map searches every format: it needs modulations_to_consider == the number of modulations")
+        if rates is None:
+            if c.bit_rate_mode != 0:
+                raise ValueError("rates=None needs discrete bit rates: pass rates")
+            R, rates_arr = int(c.n_bit_rates), None
+        else:
+            if isinstance(weights, str):
+                raise ValueError('weights="traffic" describes the configured bit rates: with rates pass an array or None')
+            rates_arr = np.ascontiguousarray(np.asarray(rates, np.float32).reshape(-1))
+            R = int(rates_arr.size)
+            if not 1 <= R <= nat.MAX_ADMISSION_RATES:
+                raise ValueError(f"the number of rates must lie in [1, {nat.MAX_ADMISSION_RATES}]")
+            if not np.all(np.isfinite(rates_arr)) or not np.all(rates_arr > 0):
+                raise ValueError("every rate must be finite and positive")
+        if isinstance(weights, str):
+            if weights != "traffic":
+                raise ValueError('weights must be "traffic", an array of shape (Q, R) or None')
+            weights = self.admission_weights()
+            traffic = True
+        else:
+            traffic = False
+        ncol = len(nat.ADMISSION_MAP)
+        rates_p = rates_arr.ctypes.data if rates_arr is not None else None
+        if c.io_device:
+            import torch
+            from .. import rl
+            dev = rl._device(self)
+            A = 1
+            if actions is not None:
+                if not isinstance(actions, torch.Tensor) or actions.dtype != torch.int32 or actions.device != dev:
+                    raise ValueError(f"actions must be a torch.int32 tensor on {dev}")
+                if actions.dim() == 1:
+                    actions = actions.reshape(-1, 1)
+                if actions.dim() != 2 or actions.shape[0] != B or not actions.is_contiguous():
+                    raise ValueError(f"actions must be contiguous with shape ({B}, A) or ({B},)")
+                A = int(actions.shape[1])
+                if actions.data_ptr() % 4:
+                    raise ValueError("actions must be aligned to its element size")
+            if not 1 <= A <= nat.MAX_IMPACT_ACTIONS:
+                raise ValueError(f"the number of actions per replica must lie in [1, {nat.MAX_IMPACT_ACTIONS}]")
+            if traffic:                                     # the configuration's weights, uploaded once per device
+                if getattr(self, "_admission_w", None) is None or self._admission_w.device != dev:
+                    self._admission_w = torch.from_numpy(weights).to(dev)
+                weights = self._admission_w
+            if weights is not None:
+                self._check_tensor(weights, "weights", torch.float64, (Q, R), dev)
+            if out is None:
+                raise ValueError("an io_device environment needs out, a float64 tensor of shape (B, A, 8) (detail: with an int32 and "
+                                 "a float32 tensor of shape (B, A, Q, R), as a triple)")
+            if detail and (not isinstance(out, (tuple, list)) or len(out) != 3):
+                raise ValueError("with detail, out must be the triple (summary, map, margin)")
+            sum_t, map_t, mar_t = out if detail else (out, None, None)
+            self._check_tensor(sum_t, "out" if not detail else "out[0]", torch.float64, (B, A, ncol), dev)
+            if detail:
+                self._check_tensor(map_t, "out[1]", torch.int32, (B, A, Q, R), dev)
+                self._check_tensor(mar_t, "out[2]", torch.float32, (B, A, Q, R), dev)
+            rl._check_stream(self)
+            ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)      # noqa: E731
+            self._check(self.lib.ongym_admission_map(self._h, A, ptr(actions), R, rates_p, ptr(weights), ptr(sum_t), ptr(map_t),
+                                                     ptr(mar_t)), "ongym_admission_map")
+            return out
+        if out is not None:
+            raise ValueError("out is for io_device environments; a host environment returns new arrays")
+        A = 1
+        if actions is not None:
+            if not isinstance(actions, np.ndarray) or actions.dtype != np.int32:
+                raise ValueError("actions must be a numpy int32 array")
+            if actions.ndim == 1:
+                actions = actions.reshape(-1, 1)
+            if actions.ndim != 2 or actions.shape[0] != B:
+                raise ValueError(f"actions must have shape ({B}, A) or ({B},)")
+            A = int(actions.shape[1])
+            actions = np.ascontiguousarray(actions)
+        if not 1 <= A <= nat.MAX_IMPACT_ACTIONS:
+            raise ValueError(f"the number of actions per replica must lie in [1, {nat.MAX_IMPACT_ACTIONS}]")
+        if weights is not None:
+            if not isinstance(weights, np.ndarray) or weights.dtype != np.float64 or weights.shape != (Q, R):
+                raise ValueError(f"weights must be a numpy float64 array of shape ({Q}, {R})")
+            weights = np.ascontiguousarray(weights)
+        res = np.zeros((B, A, ncol), np.float64)
+        amap = np.zeros((B, A, Q, R), np.int32) if detail else None
+        mar = np.zeros((B, A, Q, R), np.float32) if detail else None
+        self._check(self.lib.ongym_admission_map(self._h, A, actions.ctypes.data if actions is not None else None, R, rates_p,
+                                                 weights.ctypes.data if weights is not None else None, res.ctypes.data,
+                                                 amap.ctypes.data if detail else None, mar.ctypes.data if detail else None),
+                    "ongym_admission_map")
+        return (res, amap, mar) if detail else res
+
     # ---- queries (plugin API) ----------------------------------------------------------------------------------------
     def available_slots(self, replica: int, path_id: int) -> np.ndarray:
         out = np.zeros(self.holder.struct.n_slots, np.int32)

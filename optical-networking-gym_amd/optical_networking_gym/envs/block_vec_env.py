@@ -11,6 +11,8 @@ step itself is the environment's ordinary ongym_step_actions.  Conventions as QR
 * `protect_running=True`: `action_masks()` also clears every block action that would push a running lightpath that is not below
   its format's minimum_osnr now below it (BatchedQRMSAEnv.action_impact, column newly_below_minimum; reject stays allowed), and
   every info dict of `step` carries `disrupts`, that count for the action taken.  Default False: nothing changes.
+* `action_lookahead()` -> float64 [B, n_actions]: the traffic-weighted probability that the NEXT request is blocked after each
+  block action of the current observation (BatchedQRMSAEnv.admission_map); the reject column is the state as it is.
 """
 from __future__ import annotations
 
@@ -57,6 +59,17 @@ class QRMSABlockVecEnv:
         if self._mask is None:
             self._observe()
         return self._mask
+
+    def action_lookahead(self) -> np.ndarray:
+        """float64 [B, K*J + 1]: admission_map's blocking_probability (traffic weights) after each block action of the current
+        observation, decoded through its action map; the reject column is the state as it is, masked-out blocks are NaN."""
+        if self._map is None:
+            self._observe()
+        res = self.env.admission_map(np.ascontiguousarray(self._map, np.int32))
+        out = res[:, :, nat.ADMISSION_MAP.index("blocking_probability")].copy()
+        out[res[:, :, 0] >= 2] = np.nan
+        out[:, :-1][~self._mask[:, :-1]] = np.nan
+        return out
 
     def step(self, block_actions: Sequence[int]):
         if self._map is None:

@@ -598,6 +598,23 @@ class QRMSAEnv:
         out["lost"] = [int(i) for i in hit if svc[0, 0, i] == reject]
         return out
 
+    def admission_map(self, action=None) -> dict:
+        """Which requests first fit would still admit - every node pair at every configured bit rate - now (action None) or
+        after `step(action)` were taken (BatchedQRMSAEnv.admission_map, with the configuration's traffic weights): a dict with
+        the keys of nat.ADMISSION_MAP (the status and the counts are ints where they are defined), plus `blocked`, a list of
+        (source, destination, bit rate, reason) with the topology's node names and the reason "spectrum" or "qot"."""
+        acts = None if action is None else np.array([[int(action)]], np.int32)
+        row, amap, _ = self._dev.admission_map(acts, detail=True)
+        c = self._dev.holder.struct
+        reject = c.k_paths * c.n_mods * c.n_slots
+        whole = ("status", "admitted", "blocked_no_spectrum", "blocked_qot", "detoured")
+        out = {k: (int(v) if k in whole and not np.isnan(v) else float(v)) for k, v in zip(nat.ADMISSION_MAP, row[0, 0])}
+        rates = self._dev.holder.bit_rates
+        out["blocked"] = [(self._nodes[s], self._nodes[d], float(rates[r]), "spectrum" if amap[0, 0, q, r] == reject else "qot")
+                          for q, (s, d) in enumerate(self._dev.admission_pairs) for r in range(amap.shape[3])
+                          if amap[0, 0, q, r] >= reject]
+        return out
+
     def close(self):
         if self.file_stats is not None:
             self.file_stats.close()
