@@ -476,6 +476,48 @@ int ongym_failure_impact(ongym_env *env, int32_t n_fail, const int32_t *links, d
 int ongym_admission_map(ongym_env *env, int32_t n_actions, const int32_t *actions, int32_t n_rates, const float *rates,
                         const double *weights, double *summary_out, int32_t *map_out, float *margin_out);
 
+/* Playouts: per replica, per candidate action of a list and per sample, the candidate applied to the pending request and then
+ * `horizon` requests decided by a policy, on a private copy of the replica - the leaf evaluation of a tree search, the rollout
+ * algorithm of policy improvement, an n-step baseline (A = n_actions, H = horizon, R = n_samples, C = capacity).
+ * Every (replica b, action a, sample r) is ONE independent scenario on the replica's current state.  By definition it is what
+ * these calls would do to a copy of the replica:
+ *   1. the stream is replaced as ongym_seed_base with seed + r and the environment's replica_base replaces it: the key becomes
+ *      the stream key of (seed + r, replica_base + b) (include/ongym_traffic.h), the request counter 0.  The pending request, the
+ *      clock and everything else stay.  With ONGYM_PLAYOUT_OWN_STREAM in `flags` the replica's own source continues from its
+ *      own position instead - its device generator or its trace, i.e. the true future; R must then be 1, `seed` is ignored.
+ *   2. the candidate is applied as ongym_step_actions applies actions[b][a] (same decoding, same GN evaluation, same
+ *      bookkeeping).  An index < 0, or actions == NULL (only with A = 1): `policy` decides the pending request as well.
+ *   3. H iterations of ongym_step_policy with `policy` follow.
+ * The A candidates of a replica see the same future for the same r (common random numbers).  The scenario ends early after a
+ * step whose record would have terminated = 1, with or without cfg.auto_reset - a playout never crosses an episode boundary -
+ * and when the source has no further request (trace exhausted).
+ * playout_out float64 [batch][A][R][8]:
+ *   0 status              0 the action was applied (accepted, or the reject action: a real choice, the future proceeds)
+ *                         1 the policy decided the pending request
+ *                         2 the step would answer "retry" (slots not free, no such route or format)
+ *                         3 the step would flag a QoT error
+ *                         4 the replica has no pending request
+ *                         status >= 2: columns 1-7 are NaN, nothing is played
+ *   1 first_accepted      `accepted` of the first step's record (0 for a reject, capacity overflow included)
+ *   2 steps               policy iterations that ran after the first step (<= H)
+ *   3 accepted            iterations among them whose record has accepted = 1
+ *   4 blocked             the others (columns 3 + 4 = column 2)
+ *   5 bit_rate_accepted   sum of the accepted requests' bit rates over those iterations, Gb/s, added in step order
+ *   6 bit_rate_requested  sum over the requests those iterations decided (the request the last iteration drew is not decided
+ *                         and does not count)
+ *   7 active_end          `active` of the last record that ran
+ * Refused with ONGYM_E_ARG: A outside 1..256, R outside 1..64, H outside 1..4096, A R > 4096, NULL actions with A != 1, NULL
+ * playout_out, unknown flags, ONGYM_PLAYOUT_OWN_STREAM with R != 1, n_mods_consider < n_mods.  With ONGYM_E_LIMIT: a policy
+ * other than first fit (0) or load balancing (1) (the kernel is instantiated for these two), cfg.defragmentation or
+ * cfg.track_service_ids (their step writes the move log and statistics in memory).  With ONGYM_E_STATE: no request source; a
+ * trace source without ONGYM_PLAYOUT_OWN_STREAM.
+ * Read-only: no replica state, statistic, work counter, random-number position or disrupted flag changes.  Buffers: host
+ * buffers (staged through a device buffer grown on demand; the call synchronises), or device buffers with cfg.io_device (then
+ * the call only launches on the environment's stream and nothing synchronises).  ongym_last_kernel_ms times the kernel. */
+enum { ONGYM_PLAYOUT_OWN_STREAM = 1 };
+int ongym_playout(ongym_env *env, int32_t n_actions, const int32_t *actions, int32_t horizon, int32_t policy,
+                  int32_t n_samples, uint64_t seed, int32_t flags, double *playout_out);
+
 /* One uniformly random VALID action per replica from an action mask [batch][k_paths*Mc*n_slots + 1] (as ongym_observe
  * writes it): what gymnasium's `action_space.sample(mask=info["mask"])` does on the reference's Discrete action space
  * (qrmsa.pyx:319-321; wrappers/qrmsa_gym.py:74-75 hands the mask out) - the masked random policy that exercises the

@@ -1421,7 +1421,10 @@ __device__ __forceinline__ void release_due_defrag(Ctx &c, float now) {
 
 // ---- one request: apply the choice (envs/qrmsa.pyx:838-1065) ----------------------------------------------------
 // outcome: 0 = accept & provision, 1 = reject action, 2 = retry (slots busy), 3 = QoT error
-template <bool R32, bool DEFRAG>
+// LOCAL (k_playout, ongym_playout.hpp): the wavefront works on a private LDS copy that is never stored back and stops at the
+// terminal step, so the terminal snapshot (the step's only store to global memory without DEFRAG) and the auto reset are left
+// out.  False in every step kernel: nothing changes there.
+template <bool R32, bool DEFRAG, bool LOCAL = false>
 __device__ __forceinline__ void apply_step(Ctx &c, const Choice &ch, int outcome, ongym_step_rec *rec) {
     const Params &P = c.P;
     DevEnv *e = c.e;
@@ -1503,7 +1506,7 @@ __device__ __forceinline__ void apply_step(Ctx &c, const Choice &ch, int outcome
         }
         // the info dict is computed before the next request is drawn (:996-1050); the step terminates the episode
         // iff that draw makes episode_services_processed reach episode_length (:1056)
-        if (s.episode_services_processed + 1 == P.episode_length) { flush_osnr(c); snapshot_terminal(c); }
+        if (!LOCAL && s.episode_services_processed + 1 == P.episode_length) { flush_osnr(c); snapshot_terminal(c); }
         if (rec) *rec = r;
     }
     if (outcome == 0) {
@@ -1530,7 +1533,7 @@ __device__ __forceinline__ void apply_step(Ctx &c, const Choice &ch, int outcome
         if (rec) { rec->active = c.active; rec->terminated = (uint8_t)terminated; }
     }
     c.active_sum += c.active;
-    if (terminated && P.auto_reset) { wave_sync(); reset_env(c); }
+    if (!LOCAL && terminated && P.auto_reset) { wave_sync(); reset_env(c); }
 }
 
 

@@ -29,6 +29,7 @@
 #include "ongym_impact.hpp"        // effect of candidate actions on the running lightpaths (ongym_action_impact)
 #include "ongym_failure.hpp"       // single-link failures and first-fit restoration (ongym_failure_impact)
 #include "ongym_admission.hpp"     // first-fit admission of every node pair and bit rate (ongym_admission_map)
+#include "ongym_playout.hpp"       // candidate actions followed by H policy steps on a private copy (ongym_playout)
 
 using namespace ongym;
 
@@ -540,6 +541,10 @@ static size_t admission_part_rows(const Params &P) {
     return std::min<size_t>(2 * kAdmissionFill, (size_t)P.batch * kMaxAdmissionActions * 16);
 }
 
+// Grid order of k_playout: the A * R wavefronts of a replica re-read its state, so either they are adjacent in
+// dispatch order or the replicas are fastest, as in k_failure_impact.  Both are measured in profiles/r17_playout.txt.
+constexpr int kPlayoutByReplica = 0;
+
 // At the end of create, after every allocation of build(): the buffer of the groups' partial sums (so that no call allocates, and
 // the state arrays lie where they lay without it), and the measurement knob
 static int admission_prepare(ongym_env *env) {
@@ -549,6 +554,8 @@ static int admission_prepare(ongym_env *env) {
     st.bytes = bytes;
     const char *g = std::getenv("ONGYM_ADMISSION_GROUPS");
     env->admission_groups = g ? std::max(0, std::atoi(g)) : 0;
+    const char *o = std::getenv("ONGYM_PLAYOUT_ORDER");
+    env->playout_by_replica = o ? std::atoi(o) != 0 : kPlayoutByReplica;
     return 0;
 }
 
@@ -1576,6 +1583,50 @@ int ongym_admission_map(ongym_env *env, int32_t n_actions, const int32_t *action
                            (const double *)part, sp[0].as<double>());
         HIP_TRY(env, hipGetLastError());
         return 0;
+    });
+    return rc ? rc : stage_close(env, sp);
+}
+
+int ongym_playout(ongym_env *env, int32_t n_actions, const int32_t *actions, int32_t horizon, int32_t policy, int32_t n_samples,
+                  uint64_t seed, int32_t flags, double *playout_out) {
+    if (!env) return ONGYM_E_ARG;
+    if (!playout_out) return fail_arg(env, "null playout_out");
+    const Params &P = env->P;
+    if (n_actions < 1 || n_actions > kMaxPlayoutActions) return fail_arg(env, "n_actions must lie in [1, 256]");
+    if (n_samples < 1 || n_samples > kMaxPlayoutSamples) return fail_arg(env, "n_samples must lie in [1, 64]");
+    if (horizon < 1 || horizon > kMaxPlayoutHorizon) return fail_arg(env, "horizon must lie in [1, 4096]");
+    if (n_actions * n_samples > kMaxPlayoutScenarios) return fail_arg(env, "n_actions * n_samples must not exceed 4096");
+    if (!actions && n_actions != 1) return fail_arg(env, "null actions: n_actions must be 1");
+    if (flags & ~ONGYM_PLAYOUT_OWN_STREAM) return fail_arg(env, "unknown flags");
+    const bool own = (flags & ONGYM_PLAYOUT_OWN_STREAM) != 0;
+    if (own && n_samples != 1) return fail_arg(env, "ONGYM_PLAYOUT_OWN_STREAM: the replica's own future is one future, n_samples must be 1");
+    if (P.n_mods_consider < P.n_mods)
+        return fail_arg(env, "the playout's policies search every format: it needs modulations_to_consider == n_mods");
+    if (policy != ONGYM_POLICY_FIRST_FIT && policy != ONGYM_POLICY_LOAD_BALANCING)
+        return fail_arg(env, "policy: the playout kernel is instantiated for first fit (0) and load balancing (1) only", ONGYM_E_LIMIT);
+    if (P.track_ids)
+        return fail_arg(env, "cfg.defragmentation / cfg.track_service_ids: their step writes the move log and the replica's "
+                             "statistics in memory, a playout must not", ONGYM_E_LIMIT);
+    if (!env->has_source) return need_source(env);
+    if (P.req_mode == kReqTrace && !own)
+        return fail_arg(env, "seed: the request source is a trace, which a playout continues only with ONGYM_PLAYOUT_OWN_STREAM",
+                        ONGYM_E_STATE);
+    const size_t lds = lds_bytes(P);
+    if (lds > 160 * 1024) return fail_arg(env, "the playout kernel's LDS block exceeds 160 KiB: lower capacity", ONGYM_E_LIMIT);
+    HIP_TRY(env, hipSetDevice(env->cfg.device));
+    const size_t B = (size_t)P.batch, A = (size_t)n_actions, R = (size_t)n_samples;
+    Span sp[] = {{playout_out, B * A * R * kPlayout * sizeof(double), kOut}, {actions, B * A * sizeof(int32_t), kIn}};   // staging: playout_out | actions
+    int rc;
+    if ((rc = stage_open(env, env->stage[kStagePlayout], sp))) return rc;
+    const int by_replica = env->playout_by_replica;
+    const dim3 grid = by_replica ? dim3(P.batch, (unsigned)(A * R)) : dim3((unsigned)(B * A * R));
+    rc = timed_launch(env, [&] {
+        return with_layout(P, [&](auto UA, auto R32) {     // attenuation and the stored record codec
+            return dispatch<int, ONGYM_POLICY_LOAD_BALANCING, ONGYM_POLICY_FIRST_FIT>(policy, [&](auto POL) {
+                return launch_lds(env, k_playout<UA, R32, POL>, grid, lds, env->d_P, (int)n_actions, (int)n_samples, by_replica,
+                                  sp[1].as<const int32_t>(), (int)horizon, seed, env->replica_base, (int)own, sp[0].as<double>());
+            });
+        });
     });
     return rc ? rc : stage_close(env, sp);
 }

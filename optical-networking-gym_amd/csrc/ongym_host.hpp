@@ -18,6 +18,7 @@ enum {
     kStageFailure,  // ongym_failure_impact: link_out | svc_out | links
     kStageAdmission,      // ongym_admission_map: summary | map | margin | weights | actions
     kStageAdmissionPart,  // ... and its groups' partial sums (device only, allocated at create and never grown)
+    kStagePlayout,  // ongym_playout: playout_out | actions
     kStageStep,     // ongym_step_policy, _step_actions, _step_actions_bundle (B > 256): records | actions | next actions | flags
     kStagePolicy,   // ongym_policy_actions: actions | flags
     kStageMask,     // ongym_observe (mask | obs) and ongym_sample_actions (mask | actions): ONE buffer for the action mask
@@ -62,6 +63,9 @@ struct ongym_env {
     // ongym_admission_map (ongym_admission.hpp): a message when a node pair lists different routes in its two directions
     std::string admission_pair_err;
     int admission_groups = 0;       // ONGYM_ADMISSION_GROUPS at create: wavefront groups per scenario instead of the rule's (0: the rule)
+    // ongym_playout (ongym_playout.hpp): ONGYM_PLAYOUT_ORDER at create, a measurement knob: 1 = grid with the replicas fastest,
+    // 0 = a replica's scenarios adjacent, unset = the default
+    int playout_by_replica = 0;
 };
 
 #define HIP_TRY(env, expr)                                                                               \

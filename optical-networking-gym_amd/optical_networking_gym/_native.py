@@ -43,6 +43,10 @@ FAILURE_IMPACT = ("status", "victims", "victim_capacity", "restored", "restored_
 ADMISSION_MAP = ("status", "admitted", "blocked_no_spectrum", "blocked_qot", "blocking_probability", "bit_rate_blocking",
                  "lowest_margin", "detoured")                # ongym_admission_map: summary_out entries per (replica, action)
 MAX_ADMISSION_RATES = 16                                    # ... and the longest rate list
+PLAYOUT = ("status", "first_accepted", "steps", "accepted", "blocked", "bit_rate_accepted", "bit_rate_requested",
+           "active_end")                                    # ongym_playout: playout_out entries per (replica, action, sample)
+PLAYOUT_OWN_STREAM = 1                                      # ... its flag: the replica's own source continues
+MAX_PLAYOUT_SAMPLES, MAX_PLAYOUT_SCENARIOS, MAX_PLAYOUT_HORIZON = 64, 4096, 4096   # ... and its limits (R, A R, H)
 
 _i32p, _f64p = C.POINTER(C.c_int32), C.POINTER(C.c_double)
 
@@ -240,6 +244,9 @@ def _declare(lib):
     if hasattr(lib, "ongym_admission_map"):     # (an older build named by ONGYM_HIP_LIB has none)
         lib.ongym_admission_map.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp]
         lib.ongym_admission_map.restype = C.c_int32
+    if hasattr(lib, "ongym_playout"):           # (an older build named by ONGYM_HIP_LIB has none)
+        lib.ongym_playout.argtypes = [vp, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, vp]
+        lib.ongym_playout.restype = C.c_int32
     if hasattr(lib, "ongym_sample_actions"):
         lib.ongym_sample_actions.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp]
         lib.ongym_sample_actions.restype = C.c_int32
@@ -302,7 +309,7 @@ def _declare_tail(lib, vp, skip=()):
 
 EXPORTED_SYMBOLS = (
     "ongym_create", "ongym_destroy", "ongym_seed", "ongym_seed_base", "ongym_set_requests", "ongym_reset", "ongym_reset_episode_counters", "ongym_step_policy",
-    "ongym_step_actions", "ongym_step_actions_bundle", "ongym_policy_actions", "ongym_observe", "ongym_observe_blocks", "ongym_link_metrics", "ongym_service_qot", "ongym_action_impact", "ongym_failure_impact", "ongym_admission_map", "ongym_sample_actions", "ongym_masked_categorical", "ongym_masked_categorical_backward",
+    "ongym_step_actions", "ongym_step_actions_bundle", "ongym_policy_actions", "ongym_observe", "ongym_observe_blocks", "ongym_link_metrics", "ongym_service_qot", "ongym_action_impact", "ongym_failure_impact", "ongym_admission_map", "ongym_playout", "ongym_sample_actions", "ongym_masked_categorical", "ongym_masked_categorical_backward",
     "ongym_masked_categorical_rows", "ongym_masked_categorical_backward_rows", "ongym_gae", "ongym_state_size", "ongym_state_save", "ongym_state_load", "ongym_fork", "ongym_query_available", "ongym_query_gsnr", "ongym_query_gsnr_many", "ongym_query_moves", "ongym_query_grid",
     "ongym_query_services", "ongym_query_request", "ongym_query_candidates", "ongym_query_path_free",
     "ongym_stats_get", "ongym_sync", "ongym_set_stream", "ongym_last_kernel_ms", "ongym_query_occupancy", "ongym_query_occupancy_policy",

@@ -569,6 +569,82 @@ class BatchedQRMSAEnv:
                     "ongym_admission_map")
         return (res, amap, mar) if detail else res
 
+    # ---- playouts: candidate actions followed by H policy steps (ongym_playout, include/ongym.h) ------------------------------
+    def playout(self, actions=None, horizon: int = 32, policy: int = nat.POLICY_FIRST_FIT, samples: int = 1, seed: int = 0,
+                own_stream: bool = False, out=None):
+        """What happens after each candidate action: float64 [B, A, R, 8], columns nat.PLAYOUT (status, first_accepted, steps,
+        accepted, blocked, bit_rate_accepted, bit_rate_requested, active_end).  Every (replica, action, sample r) is one scenario
+        on a private copy of the replica: the stream replaced as seed(seed + r, replica_base) replaces it, the candidate applied
+        as step() applies it, then `horizon` iterations of step_policy(policy), ending early at the end of the episode or of the
+        trace.  The candidates of a replica see the same future for the same r.  actions: int32 [B, A] (or [B]: A = 1) of full
+        step action indices for the pending request, 1 <= A <= nat.MAX_IMPACT_ACTIONS; an index < 0, or None (A = 1): the policy
+        decides the pending request too.  policy: first fit or load balancing.  samples: R, 1..nat.MAX_PLAYOUT_SAMPLES, with
+        A R <= nat.MAX_PLAYOUT_SCENARIOS.  own_stream=True continues the replica's own generator or trace instead (the true
+        future; samples must be 1, seed is ignored).  Read-only.  A host environment takes and returns numpy arrays.  An
+        io_device environment takes a torch tensor on its device and writes into `out`, on torch's current stream
+        (env.set_stream), without synchronising."""
+        c = self.holder.struct
+        B = self.batch_size
+        H, R, policy = int(horizon), int(samples), int(policy)
+        if c.n_mods_consider < c.n_mods:
+            raise ValueError("playout's policies search every format: it needs modulations_to_consider == the number of modulations")
+        if not 1 <= H <= nat.MAX_PLAYOUT_HORIZON:
+            raise ValueError(f"horizon must lie in [1, {nat.MAX_PLAYOUT_HORIZON}]")
+        if not 1 <= R <= nat.MAX_PLAYOUT_SAMPLES:
+            raise ValueError(f"samples must lie in [1, {nat.MAX_PLAYOUT_SAMPLES}]")
+        if own_stream and R != 1:
+            raise ValueError("own_stream continues the replica's one true future: samples must be 1")
+        flags = nat.PLAYOUT_OWN_STREAM if own_stream else 0
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        ncol = len(nat.PLAYOUT)
+
+        def check_A(A):
+            if not 1 <= A <= nat.MAX_IMPACT_ACTIONS:
+                raise ValueError(f"the number of actions per replica must lie in [1, {nat.MAX_IMPACT_ACTIONS}]")
+            if A * R > nat.MAX_PLAYOUT_SCENARIOS:
+                raise ValueError(f"actions x samples per replica must not exceed {nat.MAX_PLAYOUT_SCENARIOS}")
+
+        if c.io_device:
+            import torch
+            from .. import rl
+            dev = rl._device(self)
+            A = 1
+            if actions is not None:
+                if not isinstance(actions, torch.Tensor) or actions.dtype != torch.int32 or actions.device != dev:
+                    raise ValueError(f"actions must be a torch.int32 tensor on {dev}")
+                if actions.dim() == 1:
+                    actions = actions.reshape(-1, 1)
+                if actions.dim() != 2 or actions.shape[0] != B or not actions.is_contiguous():
+                    raise ValueError(f"actions must be contiguous with shape ({B}, A) or ({B},)")
+                A = int(actions.shape[1])
+                if actions.data_ptr() % 4:
+                    raise ValueError("actions must be aligned to its element size")
+            check_A(A)
+            if out is None:
+                raise ValueError(f"an io_device environment needs out, a float64 tensor of shape (B, A, R, {ncol})")
+            self._check_tensor(out, "out", torch.float64, (B, A, R, ncol), dev)
+            rl._check_stream(self)
+            self._check(self.lib.ongym_playout(self._h, A, C.c_void_p(actions.data_ptr() if actions is not None else None), H,
+                                               policy, R, C.c_uint64(seed), flags, C.c_void_p(out.data_ptr())), "ongym_playout")
+            return out
+        if out is not None:
+            raise ValueError("out is for io_device environments; a host environment returns a new array")
+        A = 1
+        if actions is not None:
+            if not isinstance(actions, np.ndarray) or actions.dtype != np.int32:
+                raise ValueError("actions must be a numpy int32 array")
+            if actions.ndim == 1:
+                actions = actions.reshape(-1, 1)
+            if actions.ndim != 2 or actions.shape[0] != B:
+                raise ValueError(f"actions must have shape ({B}, A) or ({B},)")
+            A = int(actions.shape[1])
+            actions = np.ascontiguousarray(actions)
+        check_A(A)
+        res = np.zeros((B, A, R, ncol), np.float64)
+        self._check(self.lib.ongym_playout(self._h, A, actions.ctypes.data if actions is not None else None, H, policy, R,
+                                           C.c_uint64(seed), flags, res.ctypes.data), "ongym_playout")
+        return res
+
     # ---- queries (plugin API) ----------------------------------------------------------------------------------------
     def available_slots(self, replica: int, path_id: int) -> np.ndarray:
         out = np.zeros(self.holder.struct.n_slots, np.int32)

@@ -13,6 +13,10 @@ step itself is the environment's ordinary ongym_step_actions.  Conventions as QR
   every info dict of `step` carries `disrupts`, that count for the action taken.  Default False: nothing changes.
 * `action_lookahead()` -> float64 [B, n_actions]: the traffic-weighted probability that the NEXT request is blocked after each
   block action of the current observation (BatchedQRMSAEnv.admission_map); the reject column is the state as it is.
+* `playout_lookahead(horizon, samples, seed)` -> float64 [B, n_actions]: the expected number of blocked requests among the
+  pending one and the next `horizon`, first fit deciding those, after each block action (BatchedQRMSAEnv.playout); the reject
+  column is the reject action.  `seed=None` numbers the calls on the Python side (as RolloutCollector numbers its draws): the
+  counter is not device state, neither saved by save_state nor restored by load_state.
 """
 from __future__ import annotations
 
@@ -41,6 +45,7 @@ class QRMSABlockVecEnv:
         self.env.seed(seed)
         self.protect_running = bool(protect_running)
         self._obs = self._mask = self._map = self._newly = None
+        self._playout_seed, self._playout_calls = int(seed), 0
 
     def _observe(self):
         self._obs, mask, self._map = self.env.observe_blocks(self.blocks)
@@ -68,6 +73,25 @@ class QRMSABlockVecEnv:
         res = self.env.admission_map(np.ascontiguousarray(self._map, np.int32))
         out = res[:, :, nat.ADMISSION_MAP.index("blocking_probability")].copy()
         out[res[:, :, 0] >= 2] = np.nan
+        out[:, :-1][~self._mask[:, :-1]] = np.nan
+        return out
+
+    def playout_lookahead(self, horizon: int = 32, samples: int = 4, seed=None) -> np.ndarray:
+        """float64 [B, K*J + 1]: the mean over `samples` futures of (1 - first_accepted) + blocked of BatchedQRMSAEnv.playout, the
+        expected number of blocked requests among the pending one and the next `horizon` with first fit deciding those, after
+        each block action of the current observation; the futures are common to the actions of a replica.  The reject column is
+        the reject action, masked-out blocks and actions the step would not take (status >= 2) are NaN.  seed=None: call n of
+        this object uses seed (the constructor's seed + 1) * 2^32 + n * samples, so successive calls see fresh futures; the
+        counter lives on the Python side, not in the device state."""
+        if self._map is None:
+            self._observe()
+        if seed is None:
+            seed = ((self._playout_seed + 1) << 32) + self._playout_calls * int(samples)
+            self._playout_calls += 1
+        res = self.env.playout(np.ascontiguousarray(self._map, np.int32), horizon=horizon, samples=samples, seed=seed)
+        col = nat.PLAYOUT.index
+        out = ((1.0 - res[..., col("first_accepted")]) + res[..., col("blocked")]).mean(axis=2)
+        out[(res[..., 0] >= 2).any(axis=2)] = np.nan
         out[:, :-1][~self._mask[:, :-1]] = np.nan
         return out
 

@@ -129,7 +129,7 @@ class QRMSAEnv:
                  k_paths: int = 5, file_name: str = "", blocks_to_consider: int = 1, modulations_to_consider: int = 6,
                  defragmentation: bool = False, n_defrag_services: int = 0, gen_observation: bool = True,
                  bands: object = None, device: int = 0, capacity: int = 1024, sync_views: bool = True,
-                 requests: Optional[np.ndarray] = None):
+                 requests: Optional[np.ndarray] = None, track_service_ids: bool = True):
         self.gen_observation = bool(gen_observation)
         self.defragmentation, self.n_defrag_services = bool(defragmentation), int(n_defrag_services)
         self.measure_disruptions = bool(measure_disruptions)
@@ -191,15 +191,18 @@ class QRMSAEnv:
             defragmentation=defragmentation, n_defrag_services=n_defrag_services)
         # service ids are kept on device so that calculate_osnr's skip-by-service-id (core/osnr.pyx:65) is exact also after a
         # counters-only reset; the id-tracking kernels need uniform attenuation (per-link attenuation: no ids, and the
-        # counters-only reset is then refused)
-        try:
-            self._dev = BatchedQRMSAEnv(track_service_ids=True, **dev_kw)
-            self._tracks_ids = True
-        except OngymError as exc:
-            if "uniform attenuation" not in str(exc):
-                raise
+        # counters-only reset is then refused).  track_service_ids=False asks for that mode outright: playout() needs it (the
+        # library refuses playouts on an environment that tracks ids), at the price of the counters-only reset
+        self._dev = None
+        if track_service_ids or defragmentation:
+            try:
+                self._dev = BatchedQRMSAEnv(track_service_ids=True, **dev_kw)
+            except OngymError as exc:
+                if "uniform attenuation" not in str(exc):
+                    raise
+        self._tracks_ids = self._dev is not None
+        if self._dev is None:
             self._dev = BatchedQRMSAEnv(**dev_kw)
-            self._tracks_ids = False
         if requests is not None:
             self._dev.set_requests(requests)           # trace replay (parity tests)
         else:
@@ -614,6 +617,22 @@ class QRMSAEnv:
                           for q, (s, d) in enumerate(self._dev.admission_pairs) for r in range(amap.shape[3])
                           if amap[0, 0, q, r] >= reject]
         return out
+
+    def playout(self, actions, horizon: int = 32, policy: int = nat.POLICY_FIRST_FIT, samples: int = 1, seed: int = 0,
+                own_stream: bool = False) -> list:
+        """What happens after each candidate of `actions` (step action indices for the pending request; one < 0 lets `policy`
+        decide it) when `policy` handles the next `horizon` requests (BatchedQRMSAEnv.playout): one dict per action with the
+        keys of nat.PLAYOUT, the mean over `samples` futures that all candidates share.  The status is an int; a candidate the
+        step would not take (status >= 2) has NaN everywhere else.  Nothing changes in the environment.  The library refuses
+        playouts on an environment that tracks service ids or defragments: create the environment with track_service_ids=False
+        (the counters-only reset is then refused, as it is under per-link attenuation)."""
+        if self._tracks_ids:
+            raise ValueError("playout needs an environment created with track_service_ids=False (and no defragmentation): the "
+                             "library refuses playouts where the step tracks service ids")
+        acts = np.asarray(actions, np.int32).reshape(1, -1)
+        res = self._dev.playout(acts, horizon=horizon, policy=policy, samples=samples, seed=seed, own_stream=own_stream)[0]
+        return [{k: (int(rows[0, i]) if k == "status" else float(rows[:, i].mean())) for i, k in enumerate(nat.PLAYOUT)}
+                for rows in res]
 
     def close(self):
         if self.file_stats is not None:
