@@ -147,6 +147,12 @@ __device__ __forceinline__ double wave_min_f64(double v) {     // as wave_max_f6
 //                        Measured on MI355X in round 3: 0.89x (first fit) - an fp64 16x16x4 MFMA occupies the matrix pipe for
 //                        64 clocks on gfx950 (fp64 matrix rate = vector rate), two dependent ones cost more than the 31 VALU.
 typedef double double4_t __attribute__((ext_vector_type(4)));
+// `old` operand of a masked DPP move whose unwritten lanes nobody reads: some register, defined by no instruction
+__device__ __forceinline__ int dpp_any() {
+    int x;
+    asm volatile("" : "=v"(x));     // volatile: every use gets a register of its own, not a copy of one common definition
+    return x;
+}
 __device__ __forceinline__ double wave_sum_eval(double v) {
 #if defined(ONGYM_X_MFMA_SUM)
     // A[i][k] = lane 16k + i, B = 1: D[i][j] = sum of lanes {i, i+16, i+32, i+48}; a lane's four accumulators hold four different
@@ -161,14 +167,17 @@ __device__ __forceinline__ double wave_sum_eval(double v) {
     v += dpp_f64<0x4E>(v);
     v += dpp_f64<0x141>(v);
     v += dpp_f64<0x140>(v);                 // every lane of a row holds the row's sum
+    // Only lane 63 is read.  Row 3 is written by both masked moves and lane 31, which it receives in the second, belongs to row 1,
+    // which the first one writes: what the rows outside a mask add never reaches the result, so their lanes of `b` keep whatever
+    // the register held (an `old` operand of 0 cost a v_mov_b32 per half and step: four per evaluation).
     union { double d; int i[2]; } a, b;
     a.d = v;                                // rows 1 and 3 += lane 15 of the row before (row_bcast:15, row_mask 0b1010)
-    b.i[0] = __builtin_amdgcn_update_dpp(0, a.i[0], 0x142, 0xA, 0xF, false);
-    b.i[1] = __builtin_amdgcn_update_dpp(0, a.i[1], 0x142, 0xA, 0xF, false);
+    b.i[0] = __builtin_amdgcn_update_dpp(dpp_any(), a.i[0], 0x142, 0xA, 0xF, false);
+    b.i[1] = __builtin_amdgcn_update_dpp(dpp_any(), a.i[1], 0x142, 0xA, 0xF, false);
     v += b.d;
     a.d = v;                                // rows 2 and 3 += lane 31 (row_bcast:31, row_mask 0b1100): row 3 holds the total
-    b.i[0] = __builtin_amdgcn_update_dpp(0, a.i[0], 0x143, 0xC, 0xF, false);
-    b.i[1] = __builtin_amdgcn_update_dpp(0, a.i[1], 0x143, 0xC, 0xF, false);
+    b.i[0] = __builtin_amdgcn_update_dpp(dpp_any(), a.i[0], 0x143, 0xC, 0xF, false);
+    b.i[1] = __builtin_amdgcn_update_dpp(dpp_any(), a.i[1], 0x143, 0xC, 0xF, false);
     v += b.d;
     return readlane_f64(v, 63);
 #else
@@ -176,7 +185,22 @@ __device__ __forceinline__ double wave_sum_eval(double v) {
 #endif
 }
 
+// Six v_min_f32 with a DPP source operand, in place (the steps of wave_sum_eval; the rows outside a row_mask keep their value):
+// the builtin form cost a DPP move, a canonicalising v_max_f32 and the v_min_f32 per step, and a copy before each masked step.
+// The two wait states between a vector write and a DPP read of the same register are spelled out (s_nop 1); release times are
+// never NaN, so the minimum is the same number.  (The compiler's hazard handling does not look into an asm statement.)
 __device__ __forceinline__ float wave_min_f32(float v) {       // wave-uniform result
+#ifndef ONGYM_X_BUILTIN_WAVE_MIN
+    asm("s_nop 1\n\tv_min_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\tv_min_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\tv_min_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\tv_min_f32_dpp %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\tv_min_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
+        "s_nop 1\n\tv_min_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
+        "s_nop 0"                               // and the wait state between a vector write and v_readlane
+        : "+v"(v));
+    return rlf(v, 63);
+#else
     v = fminf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true)));
     v = fminf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true)));
     v = fminf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true)));
@@ -185,6 +209,7 @@ __device__ __forceinline__ float wave_min_f32(float v) {       // wave-uniform r
     v = fminf(v, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0x142, 0xA, 0xF, false)));
     v = fminf(v, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0x143, 0xC, 0xF, false)));
     return rlf(v, 63);
+#endif
 }
 
 __device__ __forceinline__ int first_set32(uint32_t x) {
@@ -609,6 +634,17 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
         }
     };
 
+    // First fit's interferer list build reads chunks 0..3 of 64 records straight, without a loop, when every running service lies
+    // in them: unused entries are neutral, so indices 0..255 need no bounds test in a table that large.  One pinned scalar and
+    // one compare at the site: 256, or -1 for a smaller table.  (The build holds four record words at once.  Load balancing
+    // measured no gain from it, and the kernels of the other two policies spill vector registers as it is: they keep the loop.)
+    constexpr bool FOUR_LIST = POL == ONGYM_POLICY_FIRST_FIT;
+    int four_max = C >= 4 * kWave ? 4 * kWave : -1;
+    asm volatile("" : "+s"(four_max));
+    auto four_chunks = [&]() -> bool {
+        asm volatile("" : "+s"(active));        // decided where it is used: held from the top of a step, the answer costs a register pair
+        return active <= four_max;
+    };
     int ep_len = P.episode_length;          // held in a scalar register (the lean units are built without loop-invariant code motion)
     asm volatile("" : "+s"(ep_len));
     const char __attribute__((address_space(1))) *const tab = (const char __attribute__((address_space(1))) *)P.pair_tab2k;
@@ -870,6 +906,25 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
             // the gathers of the evaluation at centre c2 that follows the build (not HIGHEST_SNR, which evaluates by candidates).
             auto build_cache = [&](uint32_t mask_lo, uint32_t mask_hi, uint32_t c2, TabPair (&t)[ENT]) {
                 L = 0;
+                if (FOUR_LIST && four_chunks()) {
+                    // All four chunks of 64 records in one LDS round trip and no loop (unused entries: mask 0): four tests and
+                    // ballots, list positions from v_mbcnt on top of the running count, four EXEC-masked stores.
+                    uint2 ab[4];
+    #pragma unroll
+                    for (int c = 0; c < 4; c++) {
+                        ab[c].x = rec[c * kWave + lane].x;
+                        if (M64) ab[c].y = rec[c * kWave + lane].y;
+                    }
+    #pragma unroll
+                    for (int c = 0; c < 4; c++) {
+                        bool ov = (ab[c].x & mask_lo) != 0;
+                        if (M64) ov |= ((ab[c].y >> 23) & mask_hi) != 0;
+                        const uint64_t bal = __ballot(ov);
+                        const int p = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, (uint32_t)L));
+                        if (ov) list[p] = (uint16_t)(c * kWave + lane);
+                        L += __popcll((unsigned long long)bal);
+                    }
+                } else
                 for (int base = 0; base < active; base += 2 * kWave) {
                     const int i0 = base + lane, i1 = i0 + kWave;
                     const int i1c = min(i1, C);          // beyond the table: the neutral entry
@@ -1126,7 +1181,11 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                 return false;
             };
 
-            while (feas) {
+            // One exit, at the bottom (feas != 0 here): a success leaves by emptying the set of formats, behind an asm the compiler
+            // cannot thread into a second exit.  With `while (feas)` and `break` the unified exit block cost every pass three
+            // v_readfirstlane of undefined registers on the header and two scalar moves on the latch; this form has s_cmp + branch.
+#define FORMATS_DONE { asm volatile("s_mov_b32 %0, 0" : "=s"(feas)); continue; }
+            do {
                 const int m = 31 - __builtin_clz(feas);            // best modulation first
                 asm("s_bitset0_b32 %0, %1" : "+s"(feas) : "s"(m));
                 const int q = 8 * cur_bi + m;
@@ -1160,7 +1219,7 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                     ch_k = k; ch_m = ln & 7; ch_slot = first; ch_n = n; ch_path = path;
                     ch_mask = pmask;
                     ch_acc = ev_acc; ch_ase = ev_ase; ch_nli = ev_nli;
-                    break;
+                    FORMATS_DONE;
                 }
                 if (POL == ONGYM_POLICY_LOWEST_FRAGMENTATION) {
                     // the other starts of this format, 128 at a time, until one passes
@@ -1169,9 +1228,10 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                     FSTAMP(14);
                     const bool hit = cnt > 0 && eval_cands(cnt, nn, m, q, pr, k, path, pmask, w_nlic, w_selfa, w_lim_lo, w_lim_hi);
                     FSTAMP(15);
-                    if (hit) break;
+                    if (hit) FORMATS_DONE;
                 }
-            }
+            } while (feas);
+#undef FORMATS_DONE
             if (POL == ONGYM_POLICY_LOWEST_FRAGMENTATION && ch_k >= 0) {
                 // `env.step(action)` evaluates the GN model itself at the width the format needs (the heuristic asked for one slot
                 // more): the reference raises ValueError if that fails (envs/qrmsa.pyx:925-929) — a fused episode rejects the
