@@ -420,6 +420,38 @@ int ongym_action_impact(ongym_env *env, int32_t n_actions, const int32_t *action
  * ongym_last_kernel_ms times the kernel. */
 int ongym_failure_impact(ongym_env *env, int32_t n_fail, const int32_t *links, double *link_out, int32_t *svc_out);
 
+/* What happens when several links go down at once - two fibres, a node (all its links), a shared-risk link group (the fibres
+ * of one duct): ongym_failure_impact with a SET of failed links per scenario (F = n_sets, E = n_links, C = capacity).  None
+ * of these follows from single-link answers: a victim of link A must also avoid link B, the victims of A and B compete for the
+ * same left-over spectrum one after the other, and a lightpath that crosses both is one victim.
+ * sets uint64 [R][F][2], 1 <= F <= 65 535; R = batch with per_replica != 0, otherwise R = 1: one list shared by all replicas.
+ * Bit e & 63 of word e >> 6 fails link e (the bit order of the library's path masks).  Every (replica, column) is ONE
+ * independent scenario on the replica's current state; duplicates are allowed; the empty set and a set with a bit at an
+ * index >= E are skipped (status 1).
+ * Scenario: that of ongym_failure_impact with "contains e" read as "contains a failed link".  The victims are the running
+ * records whose route contains ANY failed link, each counted once, in ascending record index; all leave at once; restoration
+ * goes one victim after the other in record order over the routes k = 0..K-1 of the victim's node pair that contain NO
+ * failed link, formats from M-1 down, the lowest start only, the same capacity rule n' = ceil(n se[m] / se[m']), the same ASE
+ * bound, GN model (over what runs in the scenario at that moment, quirk Q12 under id tracking) and admission test; a
+ * restoration is provisioned and appended as the step does it.
+ * set_out float64 [batch][F][12]:
+ *   0-9  the columns of ongym_failure_impact's link_out, same names and meaning (5 lost_no_spectrum still includes "no eligible
+ *        route")
+ *   10 lost_no_route       the part of column 5 whose node pair has no route left at all (every route of the pair, or the pair
+ *                          itself, is gone): where the lightpaths that end at a failed node are counted
+ *   11 failed_links        number of links in the set
+ *   Status 1: columns 1-11 are NaN.  Column 1 = columns 3 + 5 + 6, column 10 <= column 5.
+ * svc_out     NULL, or int32 [batch][F][C], encoded as ongym_failure_impact's (4 F C bytes per replica: for small batches or
+ *             short lists).
+ * Refused (ONGYM_E_ARG): F out of range, NULL sets, NULL set_out, n_mods_consider < n_mods, pair lists that disagree on a
+ * route's node pair; ONGYM_E_LIMIT: the LDS block exceeds the limit (as ongym_failure_impact).
+ * Read-only: no replica state, statistic, counter (total_gn_evals included), disrupted flag, move log or random-number
+ * position changes.  Buffers: host buffers (staged through a device buffer grown on demand; the call synchronises), or device
+ * buffers with cfg.io_device (then the call only launches on the environment's stream and nothing synchronises; sets must be
+ * 8-byte aligned).  ongym_last_kernel_ms times the kernel. */
+int ongym_failure_sets(ongym_env *env, int32_t n_sets, const uint64_t *sets, int32_t per_replica, double *set_out,
+                       int32_t *svc_out);
+
 /* What the network could still carry right now: per replica and per candidate action of a list, first fit's admission decision
  * for EVERY request the traffic model can draw - every unordered node pair and every bit rate of a list - on the replica's
  * current state (N = n_nodes, K = k_paths, M = n_mods, S = n_slots, C = capacity, Q = N (N - 1) / 2, A = n_actions, R = n_rates).

@@ -27,7 +27,7 @@
 #include "ongym_metrics.hpp"       // per-link fragmentation metrics and link statistics (ongym_link_metrics)
 #include "ongym_qot.hpp"           // current QoT of every running lightpath (ongym_service_qot)
 #include "ongym_impact.hpp"        // effect of candidate actions on the running lightpaths (ongym_action_impact)
-#include "ongym_failure.hpp"       // single-link failures and first-fit restoration (ongym_failure_impact)
+#include "ongym_failure.hpp"       // link failures and first-fit restoration (ongym_failure_impact, ongym_failure_sets)
 #include "ongym_admission.hpp"     // first-fit admission of every node pair and bit rate (ongym_admission_map)
 #include "ongym_playout.hpp"       // candidate actions followed by H policy steps on a private copy (ongym_playout)
 
@@ -1528,6 +1528,33 @@ int ongym_failure_impact(ongym_env *env, int32_t n_fail, const int32_t *links, d
         return with_layout(P, [&](auto UA, auto R32) {     // attenuation and the stored record codec
             return launch_lds(env, k_failure_impact<UA, R32>, dim3(P.batch, n_fail), lds, env->d_P, (int)n_fail,
                               sp[2].as<const int32_t>(), env->d_path_pair, sp[0].as<double>(), sp[1].as<int32_t>());
+        });
+    });
+    return rc ? rc : stage_close(env, sp);
+}
+
+int ongym_failure_sets(ongym_env *env, int32_t n_sets, const uint64_t *sets, int32_t per_replica, double *set_out,
+                       int32_t *svc_out) {
+    if (!env) return ONGYM_E_ARG;
+    if (!sets || !set_out) return fail_arg(env, "null sets/set_out");
+    const Params &P = env->P;
+    if (n_sets < 1 || n_sets > kMaxFailureSets) return fail_arg(env, "n_sets must lie in [1, 65535]");
+    if (P.n_mods_consider < P.n_mods)
+        return fail_arg(env, "restoration searches every format: it needs modulations_to_consider == n_mods");
+    if (!env->path_pair_err.empty()) return fail_arg(env, env->path_pair_err.c_str());
+    const size_t lds = failure_lds_bytes(P);
+    if (lds > 160 * 1024) return fail_arg(env, "the failure kernel's LDS block exceeds 160 KiB: lower capacity", ONGYM_E_LIMIT);
+    HIP_TRY(env, hipSetDevice(env->cfg.device));
+    const size_t B = (size_t)P.batch, F = (size_t)n_sets, R = per_replica ? B : 1;
+    Span sp[] = {{set_out, B * F * kFailureSets * sizeof(double), kOut},                           // staging: set_out | sets | svc_out
+                 {sets, R * F * 2 * sizeof(uint64_t), kIn}, {svc_out, B * F * P.capacity * sizeof(int32_t), kOut}};
+    int rc;
+    if ((rc = stage_open(env, env->stage[kStageFailure], sp))) return rc;
+    rc = timed_launch(env, [&] {
+        return with_layout(P, [&](auto UA, auto R32) {     // attenuation and the stored record codec
+            return launch_lds(env, k_failure_sets<UA, R32>, dim3(P.batch, n_sets), lds, env->d_P, (int)n_sets,
+                              sp[1].as<const uint64_t>(), (int)(per_replica != 0), env->d_path_pair, sp[0].as<double>(),
+                              sp[2].as<int32_t>());
         });
     });
     return rc ? rc : stage_close(env, sp);

@@ -15,7 +15,7 @@ using ongym::Params;
 struct Stage { void *base; size_t bytes; };
 enum {
     kStageBlocks, kStageMetrics, kStageQot, kStageImpact,   // ongym_observe_blocks, _link_metrics, _service_qot, _action_impact
-    kStageFailure,  // ongym_failure_impact: link_out | svc_out | links
+    kStageFailure,  // ongym_failure_impact: link_out | svc_out | links; ongym_failure_sets: set_out | sets | svc_out
     kStageAdmission,      // ongym_admission_map: summary | map | margin | weights | actions
     kStageAdmissionPart,  // ... and its groups' partial sums (device only, allocated at create and never grown)
     kStagePlayout,  // ongym_playout: playout_out | actions

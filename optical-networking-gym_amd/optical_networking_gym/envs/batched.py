@@ -444,6 +444,96 @@ class BatchedQRMSAEnv:
                                                   svc.ctypes.data if detail else None), "ongym_failure_impact")
         return (res, svc) if detail else res
 
+    # ---- failures of link sets: dual cuts, nodes, shared-risk groups (ongym_failure_sets, include/ongym.h) ------------------
+    @staticmethod
+    def pack_link_sets(lists, n_links: int) -> np.ndarray:
+        """uint64 [F, 2] for F iterables of link indices in [0, n_links): bit e & 63 of word e >> 6 fails link e (the bit order
+        of the library's path masks).  An empty iterable gives the empty set, which failure_sets skips (status 1)."""
+        lists = list(lists)
+        out = np.zeros((len(lists), 2), np.uint64)
+        for f, links in enumerate(lists):
+            for e in links:
+                e = int(e)
+                if not 0 <= e < min(int(n_links), 128):
+                    raise ValueError(f"link index {e} of set {f} lies outside [0, {n_links})")
+                out[f, e >> 6] |= np.uint64(1 << (e & 63))
+        return out
+
+    def node_link_sets(self) -> np.ndarray:
+        """uint64 [N, 2]: per node (in table order) the set of its incident links, i.e. the node's failure"""
+        c = self.holder.struct
+        ends = np.asarray(self.holder.tables.link_nodes)
+        return self.pack_link_sets([np.flatnonzero((ends[:, 0] == v) | (ends[:, 1] == v)) for v in range(c.n_nodes)], c.n_links)
+
+    def link_pair_sets(self) -> np.ndarray:
+        """uint64 [E (E - 1) / 2, 2]: every dual cut, in the order of itertools.combinations(range(E), 2)"""
+        from itertools import combinations
+        E = self.holder.struct.n_links
+        return self.pack_link_sets(combinations(range(E), 2), E).reshape(-1, 2)
+
+    def failure_sets(self, sets, out=None, detail=False):
+        """What happens when several links fail at once: float64 [B, F, 12], columns nat.FAILURE_SETS (those of failure_impact,
+        then lost_no_route - lost with no route of the node pair left at all, as the lightpaths that end at a failed node - and
+        failed_links), one independent scenario per (replica, column): the victims are the records that cross ANY link of the
+        set, each once, and first fit restores them in record order over the routes that cross NO link of it.  sets: uint64
+        [F, 2] (one list for every replica) or [B, F, 2] (a list per replica), bit e & 63 of word e >> 6 fails link e, 1 <= F <=
+        nat.MAX_FAILURE_SETS; or a list of F link-index iterables (pack_link_sets; node_link_sets() and link_pair_sets() make
+        the usual lists).  The empty set and a set with a bit at an index >= n_links are skipped (status 1).  detail=True also
+        returns int32 [B, F, C], encoded as failure_impact's.  Read-only.  A host environment takes and returns numpy arrays.
+        An io_device environment takes a torch.int64 or torch.uint64 tensor on its device and writes into `out` (the set
+        tensor, or with detail the pair (set, svc)), on torch's current stream (env.set_stream), without synchronising."""
+        c = self.holder.struct
+        B = self.batch_size
+        if c.n_mods_consider < c.n_mods:
+            raise ValueError("failure_sets searches every format: it needs modulations_to_consider == the number of modulations")
+        ncol = len(nat.FAILURE_SETS)
+        if c.io_device:
+            import torch
+            from .. import rl
+            dev = rl._device(self)
+            wide = (torch.int64,) + ((torch.uint64,) if hasattr(torch, "uint64") else ())
+            if not isinstance(sets, torch.Tensor) or sets.dtype not in wide or sets.device != dev:
+                raise ValueError(f"sets must be a torch.int64 or torch.uint64 tensor on {dev}")
+            if (sets.dim() not in (2, 3) or sets.shape[-1] != 2 or (sets.dim() == 3 and sets.shape[0] != B)
+                    or not sets.is_contiguous()):
+                raise ValueError(f"sets must be contiguous with shape (F, 2) or ({B}, F, 2)")
+            F = int(sets.shape[-2])
+            if not 1 <= F <= nat.MAX_FAILURE_SETS:
+                raise ValueError(f"the number of link sets per replica must lie in [1, {nat.MAX_FAILURE_SETS}]")
+            if sets.data_ptr() % 8:
+                raise ValueError("sets must be aligned to its element size")
+            if out is None:
+                raise ValueError("an io_device environment needs out, a float64 tensor of shape (B, F, 12) (detail: with an int32 "
+                                 "tensor of shape (B, F, C), as a pair)")
+            if detail and (not isinstance(out, (tuple, list)) or len(out) != 2):
+                raise ValueError("with detail, out must be the pair (set, svc)")
+            set_t, svc_t = out if detail else (out, None)
+            self._check_tensor(set_t, "out" if not detail else "out[0]", torch.float64, (B, F, ncol), dev)
+            if detail:
+                self._check_tensor(svc_t, "out[1]", torch.int32, (B, F, c.capacity), dev)
+            rl._check_stream(self)
+            self._check(self.lib.ongym_failure_sets(self._h, F, C.c_void_p(sets.data_ptr()), int(sets.dim() == 3),
+                                                    C.c_void_p(set_t.data_ptr()),
+                                                    C.c_void_p(svc_t.data_ptr() if detail else None)), "ongym_failure_sets")
+            return out
+        if out is not None:
+            raise ValueError("out is for io_device environments; a host environment returns new arrays")
+        if isinstance(sets, (list, tuple)):
+            sets = self.pack_link_sets(sets, c.n_links)
+        if not isinstance(sets, np.ndarray) or sets.dtype != np.uint64:
+            raise ValueError("sets must be a numpy uint64 array or a list of link-index iterables")
+        if sets.ndim not in (2, 3) or sets.shape[-1] != 2 or (sets.ndim == 3 and sets.shape[0] != B):
+            raise ValueError(f"sets must have shape (F, 2) or ({B}, F, 2)")
+        F = int(sets.shape[-2])
+        if not 1 <= F <= nat.MAX_FAILURE_SETS:
+            raise ValueError(f"the number of link sets per replica must lie in [1, {nat.MAX_FAILURE_SETS}]")
+        sets = np.ascontiguousarray(sets)
+        res = np.zeros((B, F, ncol), np.float64)
+        svc = np.zeros((B, F, c.capacity), np.int32) if detail else None
+        self._check(self.lib.ongym_failure_sets(self._h, F, sets.ctypes.data, int(sets.ndim == 3), res.ctypes.data,
+                                                svc.ctypes.data if detail else None), "ongym_failure_sets")
+        return (res, svc) if detail else res
+
     # ---- first-fit admission of every node pair and bit rate (ongym_admission_map, include/ongym.h) ------------------------
     @property
     def admission_pairs(self) -> np.ndarray:

@@ -601,6 +601,28 @@ class QRMSAEnv:
         out["lost"] = [int(i) for i in hit if svc[0, 0, i] == reject]
         return out
 
+    def failure_sets_impact(self, links=None, node=None) -> dict:
+        """What it would do now if several links went down at once, with first-fit restoration of the lightpaths that cross
+        any of them (BatchedQRMSAEnv.failure_sets).  links: link indices or (u, v) node pairs of the topology (a dual cut, a
+        shared-risk group); node: a node name, which fails every link at the node (the lightpaths that end there are lost for
+        good: lost_no_route).  A dict shaped like failure_impact's with the keys of nat.FAILURE_SETS, `restorations` and
+        `lost`."""
+        if (links is None) == (node is None):
+            raise ValueError("pass either links or node")
+        if node is not None:
+            links = [(node, v) for v in self.topology[node]]
+        idx = [self.topology[e[0]][e[1]]["index"] if isinstance(e, (tuple, list)) else int(e) for e in links]
+        c = self._dev.holder.struct
+        row, svc = self._dev.failure_sets(self._dev.pack_link_sets([idx], c.n_links), detail=True)
+        M, S = c.n_mods, c.n_slots
+        out = {k: (float(v) if k == "lowest_margin" or np.isnan(v) else int(v)) for k, v in zip(nat.FAILURE_SETS, row[0, 0])}
+        reject = c.k_paths * M * S
+        hit = np.flatnonzero(svc[0, 0] >= 0)
+        out["restorations"] = [(int(i), int(a) // (M * S), M - 1 - (int(a) // S) % M, int(a) % S)
+                               for i, a in zip(hit, svc[0, 0, hit]) if a != reject]
+        out["lost"] = [int(i) for i in hit if svc[0, 0, i] == reject]
+        return out
+
     def admission_map(self, action=None) -> dict:
         """Which requests first fit would still admit - every node pair at every configured bit rate - now (action None) or
         after `step(action)` were taken (BatchedQRMSAEnv.admission_map, with the configuration's traffic weights): a dict with
