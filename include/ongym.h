@@ -710,6 +710,13 @@ int ongym_query_occupancy(ongym_env *env, int32_t *blocks_per_cu, int32_t *lds_b
  * balancing, highest SNR and lowest fragmentation - the four heuristics the reference benchmark selects among
  * (examples/JOCN_Benchmark_2024/graph_load.py:116-125). */
 int ongym_query_occupancy_policy(ongym_env *env, int32_t policy, int32_t *blocks_per_cu, int32_t *lds_bytes, int32_t *lean_kernel);
+/* Diagnostic, read-only: what a lean kernel fetches from the shared-link weight table (csrc/ongym_lwtab.hpp) for route `path`
+ * and an interferer whose link mask is `links` (bit l = link l; links that are not on the route do not matter).
+ * out[0] = 1 when the environment has a table (links fit one mask word, every route got a multiplier, ONGYM_FAST_NO_LWTAB
+ * was not 1 at create), else 0 and nothing else is written.  out[1] = the route's multiplier, out[2] = the index the kernel
+ * computes, out[3] = the number of index bits W; entry[0..1] = (sum w1, sum w2) as read back from device memory at the address
+ * the kernel would use.  ONGYM_E_ARG: path outside 0..n_paths-1 or a NULL pointer. */
+int ongym_query_link_weight_entry(ongym_env *env, int32_t path, uint32_t links, uint32_t out[4], double entry[2]);
 int ongym_sync(ongym_env *env);
 /* Run every later call of this environment on the CALLER's HIP stream (a hipStream_t passed as void *, e.g. PyTorch-ROCm's
  * torch.cuda.current_stream().cuda_stream) instead of the environment's own: the environment's launches are then ordered with

@@ -99,6 +99,9 @@ struct Params {
     const uint64_t *path_hash_keys; // lean M64 record codec: link mask (bits 0..40) -> path id, open addressing, 2^path_hash_bits slots
     const int32_t *path_hash_vals;
     int path_hash_bits, pad_hash;
+    // shared-link weight table (ongym_lwtab.hpp): lies in pair_tab2k's allocation, right behind the pair table, so that the
+    // lean kernels gather from both through one base address.  lw_tab_bytes == 0: no table (PathRec then carries no multiplier)
+    uint32_t lw_tab_off, lw_tab_bytes;
     const double *pair_tab2k;       // the pair table with a row pitch of 2048 entries: [tab_nmax][2048][2]
     const double *pair_tabp;        // the same rows split by the parity of the distance: [tab_nmax][2][1024][2], entry (d & 1, d >> 1).
                                     // Candidate centres of one format are two half slots apart: consecutive candidates then

@@ -55,6 +55,9 @@ constexpr int kNearHalfSlots = 32;   // candidate-lane evaluation: interferers t
 // ---- path record (8 dwords, 32-byte aligned: one s_load_dwordx8) -------------------------------------------------------
 struct PathRec {
     uint32_t hops, mask_lo, mask_hi, id;   // mask = links of the path (bit l = link l), n_links <= 41
+    // One mask word (!M64): mask_hi would be 0 and no kernel reads `id` from the record, so the two dwords deliver the route's
+    // block of the shared-link weight table (ongym_lwtab.hpp) with the same scalar load: mask_hi = the multiplier (0: the
+    // environment has no table), id = byte offset of the block from pair_tab2k (a multiple of 32) | 32 - index bits.
     double ase, w1;                        // path_ase[id], path_w1[id]
 };
 static_assert(sizeof(PathRec) == 32, "PathRec must be 32 bytes");
@@ -82,6 +85,11 @@ __device__ __forceinline__ const __attribute__((address_space(4))) T *KC(const T
     return (const __attribute__((address_space(4))) T *)p;
 }
 
+// Policies whose one-mask-word kernels take the shared-link weight sums from the table when the environment has one.  Measured
+// on MI355X, NSFNET-320: first fit -4.9 % of the kernel time.  The others keep the link loop: load
+// balancing starts to spill vector registers at 5 waves per SIMD and gains nothing, highest SNR loses 0.3 %, and lowest
+// fragmentation's gain (0.4 % to 1.2 %) did not clear the run-to-run spread.  (The table code itself is policy-agnostic.)
+__host__ __device__ constexpr bool fast_lw_policy(int policy) { return policy == ONGYM_POLICY_FIRST_FIT; }
 __host__ __device__ inline bool fast_policy_has_xlist(int policy) {
     return policy == ONGYM_POLICY_HIGHEST_SNR || policy == ONGYM_POLICY_LOWEST_FRAGMENTATION;
 }
@@ -325,7 +333,9 @@ __device__ __forceinline__ void fast_refill_trace(const Params &P, int replica, 
     }
 }
 
-template <bool M64, bool REC, int ENT, bool TRACE, int POL = ONGYM_POLICY_FIRST_FIT, bool WIDE = true>
+// LWT: shared-link weight sums come from the table of ongym_lwtab.hpp (one mask word only; the host launches these
+// instantiations when the environment has a table, fast_lw_policy() says for which policies), else from the link loop.
+template <bool M64, bool REC, int ENT, bool TRACE, int POL = ONGYM_POLICY_FIRST_FIT, bool WIDE = true, bool LWT = false>
 __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step_rec *out, unsigned char *smem) {
     ONGYM_NO_CONTRACT
 #ifdef ONGYM_STAMPS
@@ -334,6 +344,8 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
 #else
 #define FSTAMP(idx) do { } while (0)
 #endif
+    static_assert(!(LWT && M64), "the weight table needs link masks of one word");
+    constexpr bool kLwt = LWT;
     const int lane = threadIdx.x, replica = blockIdx.x;
     const int E = P.n_links, RW = P.row_words * 2, C = P.capacity, S = P.n_slots, M = P.n_mods, K = P.k_paths, N = P.n_nodes;
     DevEnv *const ge = P.env + replica;
@@ -364,6 +376,7 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
     asm volatile("v_mov_b32 %0, 0" : "=v"(vz));
 
     // ---- load: constants, bitmap, records (generic codec -> lean codec) ----
+    if (!kLwt)      // (the table instantiations never read lw)
     for (int i = lane; i <= E; i += kWave) { lw[2 * i] = i < E ? G(P.link_w1)[i] : 0.0; lw[2 * i + 1] = i < E ? G(P.link_w2)[i] : 0.0; }
     if (lane < kMaxMods) phi[lane] = lane < M ? P.mod_phi53[lane] : 0.0;
     if (POL == ONGYM_POLICY_LOWEST_FRAGMENTATION)
@@ -766,7 +779,7 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
         // The routes of the request.  FIRST_FIT walks them in order and stops at the first that serves the request; the other
         // policies look at all of them, so their ids and records are fetched together (lane k = k-th route).
         int v_path = -1, v_rank = lane, nk = K;
-        uint32_t v_hops = 1, v_mlo = 0, v_mhi = 0;
+        uint32_t v_hops = 1, v_mlo = 0, v_mhi = 0, v_lwl = 0;      // (LWT: v_mhi / v_lwl = the weight table's multiplier / block)
         double v_ase = 0.0, v_w1 = 0.0;
         if (POL != ONGYM_POLICY_FIRST_FIT) {
             if (lane < K) {
@@ -774,6 +787,7 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                 if (v_path >= 0) {
                     const auto *g = G(reinterpret_cast<const PathRec *>(P.path_rec)) + v_path;
                     v_hops = g->hops; v_mlo = g->mask_lo; v_mhi = g->mask_hi; v_ase = g->ase; v_w1 = g->w1;
+                    if (kLwt) v_lwl = g->id;
                 }
             }
             nk = __popcll((unsigned long long)__ballot(v_path >= 0));    // a pair's routes come first, -1 entries after them
@@ -859,6 +873,14 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
             const uint64_t pmask = mask_of(pr);
             uint32_t runs = path_and(pmask);
             FSTAMP(1);
+            // the route's block of the shared-link weight table (PathRec)
+            uint32_t lw_mult = 0, lw_loc = 0;
+            if (kLwt) {
+                if (POL == ONGYM_POLICY_FIRST_FIT) { lw_mult = pr.mask_hi; lw_loc = pr.id; }
+                else { lw_mult = rl(v_mhi, k); lw_loc = rl(v_lwl, k); }
+            }
+            // byte offset (from the pair table) of the entry of link subset `mm` of the route: multiply, shift, address
+            auto lw_off = [&](uint32_t mm) -> uint32_t { return (lw_loc & ~31u) + (((mm * lw_mult) >> (lw_loc & 31u)) << 4); };
             int r_len = 1;
             // (declared per route: nothing of the cache is live across routes or steps)
             // the interferers of ONE route, cached in registers (lane j + 64 e = entry j of the list); `L` = their number
@@ -870,8 +892,13 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
             // weights of the links that record `ab` shares with the route, summed in link order; returns their number
             auto link_weights = [&](const uint2 ab, uint32_t mask_lo, uint32_t mask_hi, double &w1o, double &w2o) -> int {
                 uint32_t mm = ab.x & mask_lo;
-                double w1 = 0.0, w2 = 0.0;
                 int terms = __popc(mm);
+                if (kLwt) {        // no shared link: the empty subset, index 0, entry (0, 0)
+                    const TabPair w = load_pair(tab, lw_off(mm));
+                    w1o = w.x; w2o = w.y;
+                    return terms;
+                }
+                double w1 = 0.0, w2 = 0.0;
                 while (mm) { const int l = __ffs(mm) - 1; mm &= mm - 1; w1 += lw[2 * l]; w2 += lw[2 * l + 1]; }
                 if (M64) {
                     uint32_t mh = (ab.y >> 23) & mask_hi;
@@ -966,6 +993,19 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                     }
     #pragma unroll
                     for (int e = 0; e < NG; e++) ph[e] = phi[(ab[e].y >> 11) & 7u];
+                    if (kLwt) {      // the weight gathers go out with the pair gathers, one wait for both
+                        TabPair wt[NG];
+    #pragma unroll
+                        for (int e = 0; e < NG; e++) {
+                            const uint32_t mm = ab[e].x & mask_lo;
+                            e_terms += __popc(mm);
+                            wt[e] = load_pair(tab, lw_off(mm));
+                        }
+                        if (POL != ONGYM_POLICY_HIGHEST_SNR) gather(c2, t);
+    #pragma unroll
+                        for (int e = 0; e < NG; e++) { e_w1[e] = wt[e].x; e_pw2[e] = ph[e] * wt[e].y; }
+                        return;
+                    }
                     if (POL != ONGYM_POLICY_HIGHEST_SNR) gather(c2, t);
     #pragma unroll
                     for (int e = 0; e < NG; e++) {

@@ -19,6 +19,7 @@
 #include "ongym_device.hpp"
 #include "ongym_host.hpp"
 #include "ongym_fast.hpp"      // fast_lds_bytes, PathRec (the kernels themselves: ongym_fast.hip)
+#include "ongym_lwtab.hpp"     // shared-link weight table of the lean kernels, built at create
 #include "ongym_scored.hpp"
 #include "ongym_policy_head.hpp"   // masked categorical action head (ongym_masked_categorical)
 #include "ongym_gae.hpp"           // GAE over a rollout (ongym_gae)
@@ -792,6 +793,8 @@ static int build(ongym_env *env, const ongym_config *c) {
 
     // the pair table once more with a row pitch of 2048 entries (index = row << 11 | distance: one address instruction);
     // used by the lean first-fit kernel and by the observation field builder
+    LwTable lwt;
+    P.lw_tab_off = 0; P.lw_tab_bytes = 0;
     if (!host_tab.empty() && P.tab_stride < kTabPitch && (size_t)P.tab_nmax * kTabPitch * 16 <= ((size_t)64 << 20)) {
         std::vector<double> t2((size_t)P.tab_nmax * kTabPitch * 2, 0.0);
         for (int nk = 0; nk < P.tab_nmax; nk++)
@@ -799,6 +802,18 @@ static int build(ongym_env *env, const ongym_config *c) {
                 t2[((size_t)nk * kTabPitch + d) * 2] = host_tab[(size_t)nk * P.tab_stride + d].x;
                 t2[((size_t)nk * kTabPitch + d) * 2 + 1] = host_tab[(size_t)nk * P.tab_stride + d].y;
             }
+        // ... and behind it the shared-link weight table of the lean kernels (ongym_lwtab.hpp), when the links fit one mask word.
+        // One allocation: the kernels gather from both tables through the same base register.  It is freed with the pair table.
+        const char *no_lw = std::getenv("ONGYM_FAST_NO_LWTAB");
+        if (P.rec32 && E <= 32 && !(no_lw && no_lw[0] == '1')) {
+            std::vector<uint32_t> m32((size_t)NP);
+            for (int p = 0; p < NP; p++) m32[(size_t)p] = (uint32_t)mask[2 * p];
+            lwt = lw_build(m32, w1.data(), w2.data(), t2.size() * 8);
+            if (lwt.ok) {
+                P.lw_tab_off = (uint32_t)(t2.size() * 8); P.lw_tab_bytes = (uint32_t)(lwt.entries.size() * 8);
+                t2.insert(t2.end(), lwt.entries.begin(), lwt.entries.end());
+            }
+        }
         if ((rc = upload(env, t2.data(), t2.size(), &P.pair_tab2k))) return rc;
         std::vector<double> t3((size_t)P.tab_nmax * kTabPitch * 2, 0.0);
         for (int nk = 0; nk < P.tab_nmax; nk++)
@@ -855,6 +870,10 @@ static int build(ongym_env *env, const ongym_config *c) {
                 r.hops = (uint32_t)c->path_hops[p]; r.mask_lo = (uint32_t)mask[2 * p];
                 r.mask_hi = (uint32_t)(mask[2 * p] >> 32);
                 r.id = (uint32_t)p; r.ase = path_ase[(size_t)p]; r.w1 = path_w1[(size_t)p];
+                // one mask word: mask_hi is 0 and no lean kernel reads `id` from the record (first fit knows the route it fetched,
+                // the other policies take it from pair_paths), so the two dwords carry the route's weight-table multiplier and
+                // block (see PathRec) and arrive with the same scalar load.  Kernels that sum over the links ignore both.
+                if (!m64 && P.lw_tab_bytes) { r.mask_hi = lwt.mult[(size_t)p]; r.id = lwt.loc[(size_t)p]; }
             }
             const PathRec *d_recs = nullptr;
             if ((rc = upload(env, recs.data(), recs.size(), &d_recs))) return rc;
@@ -1178,6 +1197,24 @@ int ongym_query_occupancy_policy(ongym_env *env, int32_t policy, int32_t *blocks
     }
     *blocks_per_cu = nb;
     *lean_kernel = lean ? 1 : 0;
+    return ONGYM_OK;
+}
+
+int ongym_query_link_weight_entry(ongym_env *env, int32_t path, uint32_t links, uint32_t out[4], double entry[2]) {
+    if (!env || !out || !entry) return ONGYM_E_ARG;
+    if (path < 0 || path >= env->P.n_paths) return fail_arg(env, "path out of range");
+    out[0] = 0;
+    if (!env->fast_ok || env->fast_m64 || !env->P.lw_tab_bytes) return ONGYM_OK;
+    HIP_TRY(env, hipSetDevice(env->cfg.device));
+    // the record and the entry as they lie in device memory, addressed as the kernels address them
+    PathRec r;
+    HIP_TRY(env, hipMemcpy(&r, static_cast<const PathRec *>(env->P.path_rec) + path, sizeof(r), hipMemcpyDeviceToHost));
+    const uint32_t mult = r.mask_hi, loc = r.id, idx = lw_index(links, r.mask_lo, mult, loc);
+    const size_t off = (size_t)(loc & ~31u) + (size_t)idx * 16;
+    if (off < env->P.lw_tab_off || off + 16 > (size_t)env->P.lw_tab_off + env->P.lw_tab_bytes)
+        return fail_arg(env, "weight-table entry outside the table");
+    HIP_TRY(env, hipMemcpy(entry, reinterpret_cast<const char *>(env->P.pair_tab2k) + off, 16, hipMemcpyDeviceToHost));
+    out[0] = 1; out[1] = mult; out[2] = idx; out[3] = 32u - (loc & 31u);
     return ONGYM_OK;
 }
 

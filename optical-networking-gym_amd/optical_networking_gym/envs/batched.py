@@ -808,6 +808,17 @@ class BatchedQRMSAEnv:
                     "ongym_query_occupancy_policy")
         return dict(blocks_per_cu=nb.value, lds_bytes=lds.value, lean_kernel=bool(lean.value))
 
+    def link_weight_entry(self, path: int, links: int):
+        """What a lean kernel fetches from the shared-link weight table for route `path` and an interferer with link mask
+        `links`: dict(mult, index, bits, w1, w2), or None when the environment has no table."""
+        out = (C.c_uint32 * 4)()
+        entry = (C.c_double * 2)()
+        self._check(self.lib.ongym_query_link_weight_entry(self._h, int(path), int(links) & 0xFFFFFFFF, out, entry),
+                    "ongym_query_link_weight_entry")
+        if not out[0]:
+            return None
+        return dict(mult=int(out[1]), index=int(out[2]), bits=int(out[3]), w1=float(entry[0]), w2=float(entry[1]))
+
     # ---- save / restore / fork replica states (ongym_state_*, ongym_fork; include/ongym.h) -----------------------------
     # A replica's state is its network, running services, clock, pending request, request counter, stream key, parameters and
     # ongym_stats, except the total_* work counters, which stay with the destination.  Python-side counters are not device
