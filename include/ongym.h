@@ -452,6 +452,57 @@ int ongym_failure_impact(ongym_env *env, int32_t n_fail, const int32_t *links, d
 int ongym_failure_sets(ongym_env *env, int32_t n_sets, const uint64_t *sets, int32_t per_replica, double *set_out,
                        int32_t *svc_out);
 
+/* Link failures on LIVE replicas: cut a set of links per replica, let traffic continue on the degraded network, return the
+ * fibre later (E = n_links, S = n_slots, C = capacity).  ongym_failure_impact and ongym_failure_sets answer "what if" on a
+ * private copy; these three calls change the replica's own state.
+ * A failed link is a full row that no record crosses.  Nothing new is stored: link e is FAILED exactly when row e of the
+ *   bitmap has no free slot in [0, S) and no running record's route contains e.  (A healthy full link has records on it, a
+ *   healthy link without records is entirely free: the bitmap is the union of the records' provisioned ranges.)  Every step
+ *   kernel, policy, observation and mask therefore sees the link as full and places nothing on it, and no release touches
+ *   the row, because releases walk a record's own route.
+ * Cut (per replica, one set): 1. every running record whose route contains a failed link (a victim) leaves, all at once;
+ *   2. the victims are restored one after the other in record order by first fit over the routes that contain no failed
+ *   link, exactly as in ongym_failure_sets' scenario; 3. bits [0, S) of every failed row are cleared; 4. the state is stored.
+ *   Survivors keep their order, release time, id and Service.OSNR and are compacted; a restored victim is appended in victim
+ *   order with its own release time, id and disrupted flag; under id tracking its Service.OSNR becomes the restoration's GSNR
+ *   and episode_osnr_sum moves by new - old (what defragmentation does to a moved service).  A lost victim leaves as a
+ *   departure leaves: nothing is subtracted.  No statistic other than `active` (and, with ids, episode_osnr_sum) changes,
+ *   total_* included; the pending request, the clock, the stream position and the move log stay.
+ *   With ONGYM_CUT_NO_RESTORE step 2 is skipped and every victim is dropped.
+ *   Cutting an already failed link finds no victim and changes nothing.  A replica whose set is empty or has a bit at an
+ *   index >= E is left byte for byte as it was (status 1).
+ * Consequences: state save, load and fork carry failures with the bitmap.  ongym_link_metrics reports a failed link as fully
+ *   used.  The read-only analyses (action impact, failure impact and sets, admission map, playout) treat a failed link as a
+ *   full one: a route through it is "a route without spectrum", not "no route".  ongym_reset and the in-launch auto reset
+ *   rebuild the spectrum as the reference's reset does and so RETURN EVERY FIBRE: a caller who wants a failure to outlast an
+ *   episode cuts again after `terminated`.  An observation or mask taken before a cut is stale after it.
+ * sets      uint64 [batch][2] with per_replica != 0, otherwise [2] shared by all replicas; bit order of ongym_failure_sets.
+ * cut_out   float64 [batch][13]: columns 0-11 are ongym_failure_sets' set_out columns, same names, meaning and status rule;
+ *             12 dropped   victims whose restoration was not attempted: 0 without the flag; with it the victims, and
+ *                          columns 3-8 and 10 are 0
+ *           Column 1 = columns 3 + 5 + 6 + 12.  Status 1: columns 1-12 are NaN.
+ * svc_out   NULL, or int32 [batch][C] in PRE-cut record order, encoded as ongym_failure_sets' svc_out; a dropped victim gets
+ *           the reject action.
+ * index_out NULL, or int32 [batch][C]: the POST-cut record index of every pre-cut record (survivors compacted in order, the
+ *           restored appended in victim order); -1 for a lost or dropped record and at and beyond the running count.
+ * Refused (ONGYM_E_ARG): NULL sets, NULL cut_out, unknown flags, n_mods_consider < n_mods, pair lists that disagree on a
+ * route's node pair; ONGYM_E_LIMIT: the LDS block (the state block + 14 C bytes, 26 C with id tracking) exceeds 160 KiB.
+ * Buffers: host buffers (staged; the call synchronises), or device buffers with cfg.io_device (the call only launches on the
+ * environment's stream and nothing synchronises; sets must be 8-byte aligned).  ongym_last_kernel_ms times the kernel. */
+enum { ONGYM_CUT_NO_RESTORE = 1 };
+int ongym_cut_links(ongym_env *env, const uint64_t *sets, int32_t per_replica, int32_t flags,
+                    double *cut_out, int32_t *svc_out, int32_t *index_out);
+
+/* Returns fibre: of the links in the replica's set, those that are failed by the rule above get bits [0, S) of their rows set
+ * again; the others (healthy links, indices >= E) are ignored.  Only the changed rows are written; records, statistics and the
+ * request state stay.  sets as ongym_cut_links'.  repaired_out: NULL, or int32 [batch], the links returned.  Refused
+ * (ONGYM_E_ARG): NULL sets.  Buffers and timing as ongym_cut_links'. */
+int ongym_repair_links(ongym_env *env, const uint64_t *sets, int32_t per_replica, int32_t *repaired_out);
+
+/* The failed links of every replica by the rule above: failed_out uint64 [batch][2], bit e & 63 of word e >> 6 for link e.
+ * Read-only.  Refused (ONGYM_E_ARG): NULL failed_out.  Buffers and timing as ongym_cut_links'. */
+int ongym_failed_links(ongym_env *env, uint64_t *failed_out);
+
 /* What the network could still carry right now: per replica and per candidate action of a list, first fit's admission decision
  * for EVERY request the traffic model can draw - every unordered node pair and every bit rate of a list - on the replica's
  * current state (N = n_nodes, K = k_paths, M = n_mods, S = n_slots, C = capacity, Q = N (N - 1) / 2, A = n_actions, R = n_rates).

@@ -29,6 +29,7 @@
 #include "ongym_qot.hpp"           // current QoT of every running lightpath (ongym_service_qot)
 #include "ongym_impact.hpp"        // effect of candidate actions on the running lightpaths (ongym_action_impact)
 #include "ongym_failure.hpp"       // link failures and first-fit restoration (ongym_failure_impact, ongym_failure_sets)
+#include "ongym_cut.hpp"           // link failures on live replicas (ongym_cut_links, ongym_repair_links, ongym_failed_links)
 #include "ongym_admission.hpp"     // first-fit admission of every node pair and bit rate (ongym_admission_map)
 #include "ongym_playout.hpp"       // candidate actions followed by H policy steps on a private copy (ongym_playout)
 
@@ -1592,6 +1593,75 @@ int ongym_failure_sets(ongym_env *env, int32_t n_sets, const uint64_t *sets, int
             return launch_lds(env, k_failure_sets<UA, R32>, dim3(P.batch, n_sets), lds, env->d_P, (int)n_sets,
                               sp[1].as<const uint64_t>(), (int)(per_replica != 0), env->d_path_pair, sp[0].as<double>(),
                               sp[2].as<int32_t>());
+        });
+    });
+    return rc ? rc : stage_close(env, sp);
+}
+
+// The checks every call that restores victims makes before it launches (ongym_failure_sets' own)
+static int cut_refusals(ongym_env *env) {
+    const Params &P = env->P;
+    if (P.n_mods_consider < P.n_mods)
+        return fail_arg(env, "restoration searches every format: it needs modulations_to_consider == n_mods");
+    if (!env->path_pair_err.empty()) return fail_arg(env, env->path_pair_err.c_str());
+    return ONGYM_OK;
+}
+
+int ongym_cut_links(ongym_env *env, const uint64_t *sets, int32_t per_replica, int32_t flags, double *cut_out, int32_t *svc_out,
+                    int32_t *index_out) {
+    if (!env) return ONGYM_E_ARG;
+    if (!sets) return fail_arg(env, "null sets");
+    if (!cut_out) return fail_arg(env, "null cut_out");
+    if (flags & ~ONGYM_CUT_NO_RESTORE) return fail_arg(env, "unknown flags: only ONGYM_CUT_NO_RESTORE is defined");
+    if (int rc = cut_refusals(env)) return rc;
+    const Params &P = env->P;
+    const size_t lds = cut_lds_bytes(P);
+    if (lds > 160 * 1024) return fail_arg(env, "the cut kernel's LDS block exceeds 160 KiB: lower capacity", ONGYM_E_LIMIT);
+    HIP_TRY(env, hipSetDevice(env->cfg.device));
+    const size_t B = (size_t)P.batch, R = per_replica ? B : 1;
+    Span sp[] = {{cut_out, B * kCutLinks * sizeof(double), kOut}, {sets, R * 2 * sizeof(uint64_t), kIn},   // staging: cut_out | sets | svc_out | index_out
+                 {svc_out, B * P.capacity * sizeof(int32_t), kOut}, {index_out, B * P.capacity * sizeof(int32_t), kOut}};
+    int rc;
+    if ((rc = stage_open(env, env->stage[kStageCut], sp))) return rc;
+    rc = timed_launch(env, [&] {
+        return with_layout(P, [&](auto UA, auto R32) {     // attenuation and the stored record codec
+            return launch_lds(env, k_cut_links<UA, R32>, dim3(P.batch), lds, env->d_P, sp[1].as<const uint64_t>(),
+                              (int)(per_replica != 0), (int)((flags & ONGYM_CUT_NO_RESTORE) != 0), env->d_path_pair,
+                              sp[0].as<double>(), sp[2].as<int32_t>(), sp[3].as<int32_t>());
+        });
+    });
+    return rc ? rc : stage_close(env, sp);
+}
+
+int ongym_repair_links(ongym_env *env, const uint64_t *sets, int32_t per_replica, int32_t *repaired_out) {
+    if (!env) return ONGYM_E_ARG;
+    if (!sets) return fail_arg(env, "null sets");
+    const Params &P = env->P;
+    HIP_TRY(env, hipSetDevice(env->cfg.device));
+    const size_t B = (size_t)P.batch, R = per_replica ? B : 1;
+    Span sp[] = {{sets, R * 2 * sizeof(uint64_t), kIn}, {repaired_out, B * sizeof(int32_t), kOut}};   // staging: sets | repaired_out
+    int rc;
+    if ((rc = stage_open(env, env->stage[kStageCut], sp))) return rc;
+    rc = timed_launch(env, [&] {
+        return with_layout(P, [&](auto, auto R32) {     // the stored record codec
+            return launch_lds(env, k_repair_links<R32>, dim3(P.batch), 0, env->d_P, sp[0].as<const uint64_t>(),
+                              (int)(per_replica != 0), sp[1].as<int32_t>());
+        });
+    });
+    return rc ? rc : stage_close(env, sp);
+}
+
+int ongym_failed_links(ongym_env *env, uint64_t *failed_out) {
+    if (!env) return ONGYM_E_ARG;
+    if (!failed_out) return fail_arg(env, "null failed_out");
+    const Params &P = env->P;
+    HIP_TRY(env, hipSetDevice(env->cfg.device));
+    Span sp[] = {{failed_out, (size_t)P.batch * 2 * sizeof(uint64_t), kOut}};
+    int rc;
+    if ((rc = stage_open(env, env->stage[kStageCut], sp))) return rc;
+    rc = timed_launch(env, [&] {
+        return with_layout(P, [&](auto, auto R32) {     // the stored record codec
+            return launch_lds(env, k_failed_links<R32>, dim3(P.batch), 0, env->d_P, sp[0].as<uint64_t>());
         });
     });
     return rc ? rc : stage_close(env, sp);

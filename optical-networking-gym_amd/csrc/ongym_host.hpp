@@ -19,6 +19,7 @@ enum {
     kStageAdmission,      // ongym_admission_map: summary | map | margin | weights | actions
     kStageAdmissionPart,  // ... and its groups' partial sums (device only, allocated at create and never grown)
     kStagePlayout,  // ongym_playout: playout_out | actions
+    kStageCut,      // ongym_cut_links: cut_out | sets | svc_out | index_out; ongym_repair_links: sets | repaired_out; ongym_failed_links
     kStageStep,     // ongym_step_policy, _step_actions, _step_actions_bundle (B > 256): records | actions | next actions | flags
     kStagePolicy,   // ongym_policy_actions: actions | flags
     kStageMask,     // ongym_observe (mask | obs) and ongym_sample_actions (mask | actions): ONE buffer for the action mask

@@ -42,6 +42,8 @@ FAILURE_IMPACT = ("status", "victims", "victim_capacity", "restored", "restored_
                   "extra_hops", "extra_slot_hops", "lowest_margin")   # ongym_failure_impact: link_out entries per (replica, link)
 FAILURE_SETS = FAILURE_IMPACT + ("lost_no_route", "failed_links")     # ongym_failure_sets: set_out entries per (replica, link set)
 MAX_FAILURE_SETS = 65535                                              # link sets per replica in one call
+CUT_LINKS = FAILURE_SETS + ("dropped",)                               # ongym_cut_links: cut_out entries per replica
+CUT_NO_RESTORE = 1                                                    # ... its flag: every victim is dropped, none restored
 ADMISSION_MAP = ("status", "admitted", "blocked_no_spectrum", "blocked_qot", "blocking_probability", "bit_rate_blocking",
                  "lowest_margin", "detoured")                # ongym_admission_map: summary_out entries per (replica, action)
 MAX_ADMISSION_RATES = 16                                    # ... and the longest rate list
@@ -246,6 +248,13 @@ def _declare(lib):
     if hasattr(lib, "ongym_failure_sets"):      # (an older build named by ONGYM_HIP_LIB has none)
         lib.ongym_failure_sets.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp]
         lib.ongym_failure_sets.restype = C.c_int32
+    if hasattr(lib, "ongym_cut_links"):         # (an older build named by ONGYM_HIP_LIB has none)
+        lib.ongym_cut_links.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, vp]
+        lib.ongym_cut_links.restype = C.c_int32
+        lib.ongym_repair_links.argtypes = [vp, vp, C.c_int32, vp]
+        lib.ongym_repair_links.restype = C.c_int32
+        lib.ongym_failed_links.argtypes = [vp, vp]
+        lib.ongym_failed_links.restype = C.c_int32
     if hasattr(lib, "ongym_admission_map"):     # (an older build named by ONGYM_HIP_LIB has none)
         lib.ongym_admission_map.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp]
         lib.ongym_admission_map.restype = C.c_int32
@@ -317,7 +326,7 @@ def _declare_tail(lib, vp, skip=()):
 
 EXPORTED_SYMBOLS = (
     "ongym_create", "ongym_destroy", "ongym_seed", "ongym_seed_base", "ongym_set_requests", "ongym_reset", "ongym_reset_episode_counters", "ongym_step_policy",
-    "ongym_step_actions", "ongym_step_actions_bundle", "ongym_policy_actions", "ongym_observe", "ongym_observe_blocks", "ongym_link_metrics", "ongym_service_qot", "ongym_action_impact", "ongym_failure_impact", "ongym_failure_sets", "ongym_admission_map", "ongym_playout", "ongym_sample_actions", "ongym_masked_categorical", "ongym_masked_categorical_backward",
+    "ongym_step_actions", "ongym_step_actions_bundle", "ongym_policy_actions", "ongym_observe", "ongym_observe_blocks", "ongym_link_metrics", "ongym_service_qot", "ongym_action_impact", "ongym_failure_impact", "ongym_failure_sets", "ongym_cut_links", "ongym_repair_links", "ongym_failed_links", "ongym_admission_map", "ongym_playout", "ongym_sample_actions", "ongym_masked_categorical", "ongym_masked_categorical_backward",
     "ongym_masked_categorical_rows", "ongym_masked_categorical_backward_rows", "ongym_gae", "ongym_state_size", "ongym_state_save", "ongym_state_load", "ongym_fork", "ongym_query_available", "ongym_query_gsnr", "ongym_query_gsnr_many", "ongym_query_moves", "ongym_query_grid",
     "ongym_query_services", "ongym_query_request", "ongym_query_candidates", "ongym_query_path_free",
     "ongym_stats_get", "ongym_sync", "ongym_set_stream", "ongym_last_kernel_ms", "ongym_query_occupancy", "ongym_query_occupancy_policy",

@@ -534,6 +534,130 @@ class BatchedQRMSAEnv:
                                                 svc.ctypes.data if detail else None), "ongym_failure_sets")
         return (res, svc) if detail else res
 
+    # ---- link failures on live replicas (ongym_cut_links, ongym_repair_links, ongym_failed_links, include/ongym.h) ----------
+    def _one_set_per_replica(self, sets, what: str):
+        """(sets as the library takes them, per_replica) for one link set per replica: uint64 [2] (shared) or [B, 2], or B
+        link-index iterables (pack_link_sets); on an io_device environment a torch.int64 / torch.uint64 tensor on its device"""
+        c = self.holder.struct
+        B = self.batch_size
+        if c.io_device:
+            import torch
+            from .. import rl
+            dev = rl._device(self)
+            wide = (torch.int64,) + ((torch.uint64,) if hasattr(torch, "uint64") else ())
+            if not isinstance(sets, torch.Tensor) or sets.dtype not in wide or sets.device != dev:
+                raise ValueError(f"sets must be a torch.int64 or torch.uint64 tensor on {dev}")
+            if tuple(sets.shape) not in ((2,), (B, 2)) or not sets.is_contiguous():
+                raise ValueError(f"sets must be contiguous with shape (2,) or ({B}, 2)")
+            if sets.data_ptr() % 8:
+                raise ValueError("sets must be aligned to its element size")
+            return sets, int(sets.dim() == 2)
+        if isinstance(sets, (list, tuple)):
+            if len(sets) != B:
+                raise ValueError(f"{what} takes one link-index iterable per replica ({B})")
+            sets = self.pack_link_sets(sets, c.n_links)
+        if not isinstance(sets, np.ndarray) or sets.dtype != np.uint64:
+            raise ValueError("sets must be a numpy uint64 array or a list of link-index iterables, one per replica")
+        if sets.shape not in ((2,), (B, 2)):
+            raise ValueError(f"sets must have shape (2,) or ({B}, 2)")
+        return np.ascontiguousarray(sets), int(sets.ndim == 2)
+
+    def cut_links(self, sets, restore=True, out=None, detail=False):
+        """Fail a set of links on every replica ITSELF (failure_sets only asks "what if"): float64 [B, 13], columns
+        nat.CUT_LINKS (failure_sets' twelve, then dropped).  The records that cross a failed link leave, first fit restores
+        them one after the other in record order over the routes clear of the set (restore=False: none is tried, every victim
+        is dropped), the failed rows lose every free slot and the state is stored: from then on every step, policy,
+        observation and mask sees those links as full and nothing is placed on them, until repair_links returns them or a
+        reset (reset(), or the auto reset at the end of an episode) rebuilds the spectrum.  A failed link is a full row that no
+        record crosses: nothing else is stored, so save_state, load_state and fork carry failures.  An observation or mask
+        taken before the call is stale after it.  sets: uint64 [2] (one set for every replica) or [B, 2], or B link-index
+        iterables (pack_link_sets); the empty set and a set with a bit at an index >= n_links leave the replica untouched
+        (status 1).  detail=True also returns (svc, index), both int32 [B, C] in pre-cut record order: svc encoded as
+        failure_sets' (a dropped victim gets the reject action), index the post-cut record index (-1: lost, dropped, or not
+        running).  A host environment takes and returns numpy arrays.  An io_device environment takes a torch.int64 or
+        torch.uint64 tensor on its device and writes into `out` (the cut tensor, or with detail the triple (cut, svc,
+        index)), on torch's current stream (env.set_stream), without synchronising."""
+        c = self.holder.struct
+        B = self.batch_size
+        if c.n_mods_consider < c.n_mods:
+            raise ValueError("cut_links searches every format: it needs modulations_to_consider == the number of modulations")
+        ncol = len(nat.CUT_LINKS)
+        flags = 0 if restore else nat.CUT_NO_RESTORE
+        if c.io_device:
+            import torch
+            from .. import rl
+            sets, per = self._one_set_per_replica(sets, "cut_links")
+            dev = rl._device(self)
+            if out is None:
+                raise ValueError("an io_device environment needs out, a float64 tensor of shape (B, 13) (detail: with two int32 "
+                                 "tensors of shape (B, C), as a triple)")
+            if detail and (not isinstance(out, (tuple, list)) or len(out) != 3):
+                raise ValueError("with detail, out must be the triple (cut, svc, index)")
+            cut_t, svc_t, idx_t = out if detail else (out, None, None)
+            self._check_tensor(cut_t, "out" if not detail else "out[0]", torch.float64, (B, ncol), dev)
+            if detail:
+                self._check_tensor(svc_t, "out[1]", torch.int32, (B, c.capacity), dev)
+                self._check_tensor(idx_t, "out[2]", torch.int32, (B, c.capacity), dev)
+            rl._check_stream(self)
+            self._check(self.lib.ongym_cut_links(self._h, C.c_void_p(sets.data_ptr()), per, flags, C.c_void_p(cut_t.data_ptr()),
+                                                 C.c_void_p(svc_t.data_ptr() if detail else None),
+                                                 C.c_void_p(idx_t.data_ptr() if detail else None)), "ongym_cut_links")
+            return out
+        if out is not None:
+            raise ValueError("out is for io_device environments; a host environment returns new arrays")
+        sets, per = self._one_set_per_replica(sets, "cut_links")
+        res = np.zeros((B, ncol), np.float64)
+        svc = np.zeros((B, c.capacity), np.int32) if detail else None
+        idx = np.zeros((B, c.capacity), np.int32) if detail else None
+        self._check(self.lib.ongym_cut_links(self._h, sets.ctypes.data, per, flags, res.ctypes.data,
+                                             svc.ctypes.data if detail else None, idx.ctypes.data if detail else None),
+                    "ongym_cut_links")
+        return (res, (svc, idx)) if detail else res
+
+    def repair_links(self, sets, out=None):
+        """Return fibre: the links of each replica's set that are failed (cut_links) get their spectrum back, entirely free;
+        healthy links of the set are ignored.  int32 [B], the links returned per replica.  sets as cut_links'.  An io_device
+        environment writes into `out`, an int32 tensor of shape (B,), on torch's current stream, without synchronising."""
+        B = self.batch_size
+        sets, per = self._one_set_per_replica(sets, "repair_links")
+        if self.holder.struct.io_device:
+            import torch
+            from .. import rl
+            if out is None:
+                raise ValueError("an io_device environment needs out, an int32 tensor of shape (B,)")
+            self._check_tensor(out, "out", torch.int32, (B,), rl._device(self))
+            rl._check_stream(self)
+            self._check(self.lib.ongym_repair_links(self._h, C.c_void_p(sets.data_ptr()), per, C.c_void_p(out.data_ptr())),
+                        "ongym_repair_links")
+            return out
+        if out is not None:
+            raise ValueError("out is for io_device environments; a host environment returns a new array")
+        n = np.zeros(B, np.int32)
+        self._check(self.lib.ongym_repair_links(self._h, sets.ctypes.data, per, n.ctypes.data), "ongym_repair_links")
+        return n
+
+    def failed_links(self, out=None):
+        """uint64 [B, 2]: the failed links of every replica, bit e & 63 of word e >> 6 for link e (pack_link_sets' order).
+        Link e is failed exactly when its row has no free slot and no running record crosses it.  Read-only.  An io_device
+        environment writes into `out`, a torch.int64 or torch.uint64 tensor of shape (B, 2), on torch's current stream."""
+        B = self.batch_size
+        if self.holder.struct.io_device:
+            import torch
+            from .. import rl
+            dev = rl._device(self)
+            wide = (torch.int64,) + ((torch.uint64,) if hasattr(torch, "uint64") else ())
+            if (not isinstance(out, torch.Tensor) or out.dtype not in wide or out.device != dev or tuple(out.shape) != (B, 2)
+                    or not out.is_contiguous() or out.data_ptr() % 8):
+                raise ValueError(f"an io_device environment needs out, a contiguous torch.int64 or torch.uint64 tensor of shape ({B}, 2) on {dev}")
+            rl._check_stream(self)
+            self._check(self.lib.ongym_failed_links(self._h, C.c_void_p(out.data_ptr())), "ongym_failed_links")
+            return out
+        if out is not None:
+            raise ValueError("out is for io_device environments; a host environment returns a new array")
+        f = np.zeros((B, 2), np.uint64)
+        self._check(self.lib.ongym_failed_links(self._h, f.ctypes.data), "ongym_failed_links")
+        return f
+
     # ---- first-fit admission of every node pair and bit rate (ongym_admission_map, include/ongym.h) ------------------------
     @property
     def admission_pairs(self) -> np.ndarray:
