@@ -651,8 +651,13 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
     // in them: unused entries are neutral, so indices 0..255 need no bounds test in a table that large.  One pinned scalar and
     // one compare at the site: 256, or -1 for a smaller table.  (The build holds four record words at once.  Load balancing
     // measured no gain from it, and the kernels of the other two policies spill vector registers as it is: they keep the loop.)
+    // With one mask word (LIST_TAIL) the straight path goes on above 256 services: chunks 4..6 follow one at a time, each behind
+    // one compare of the running count, up to 448 services.  The bound is the whole chunks of the table (at most seven), so a
+    // tail chunk lies inside the table and needs no bounds test either; beyond it, and with two mask words, the loop runs.
     constexpr bool FOUR_LIST = POL == ONGYM_POLICY_FIRST_FIT;
-    int four_max = C >= 4 * kWave ? 4 * kWave : -1;
+    constexpr bool LIST_TAIL = FOUR_LIST && !M64;
+    constexpr int kTailChunks = 7;
+    int four_max = C >= 4 * kWave ? (LIST_TAIL ? min(C & ~(kWave - 1), kTailChunks * kWave) : 4 * kWave) : -1;
     asm volatile("" : "+s"(four_max));
     auto four_chunks = [&]() -> bool {
         asm volatile("" : "+s"(active));        // decided where it is used: held from the top of a step, the answer costs a register pair
@@ -950,6 +955,20 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                         const int p = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, (uint32_t)L));
                         if (ov) list[p] = (uint16_t)(c * kWave + lane);
                         L += __popcll((unsigned long long)bal);
+                    }
+                    // The tail: records 256 and up, one chunk per compare of the running count, positions continuing from L (the
+                    // list stays in ascending record index, which decides the lane of every term).  four_max keeps chunk c inside
+                    // the table.  (Chunks 4..6 in one round trip hold three more words: that build spilled a vector register.)
+                    if (LIST_TAIL && active > 4 * kWave) {
+    #pragma unroll
+                        for (int c = 4; c < kTailChunks; c++) {
+                            if (c > 4 && active <= c * kWave) break;
+                            const bool ov = (rec[c * kWave + lane].x & mask_lo) != 0;
+                            const uint64_t bal = __ballot(ov);
+                            const int p = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, (uint32_t)L));
+                            if (ov) list[p] = (uint16_t)(c * kWave + lane);
+                            L += __popcll((unsigned long long)bal);
+                        }
                     }
                 } else
                 for (int base = 0; base < active; base += 2 * kWave) {
@@ -1470,7 +1489,32 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
         // third of the requests arrive before it (departures per inter-arrival time are Poisson with mean ~1): no scan then
         if (v_at >= next_rel) {
             float keep_min = INFINITY;
-        for (int top = ((active + kWave - 1) / kWave) - 1; top >= 0; top -= 4) {
+            int top = ((active + kWave - 1) / kWave) - 1;
+        if (!M64) {
+            // One mask word: whole trips of four chunks while four are left, with no clamp and no select, then the chunks that
+            // remain (at most three) one at a time.  No chunk is read twice and a single chunk never pays a four-chunk trip; the
+            // order of the departures is the loop's (highest chunk first, highest index first).
+            for (; top >= 3; top -= 4) {
+                const float r0 = rr[top * kWave + lane], r1 = rr[(top - 1) * kWave + lane];
+                const float r2 = rr[(top - 2) * kWave + lane], r3 = rr[(top - 3) * kWave + lane];
+                const uint64_t b0 = __ballot(r0 <= v_at), b1 = __ballot(r1 <= v_at), b2 = __ballot(r2 <= v_at), b3 = __ballot(r3 <= v_at);
+                keep_min = fminf(fminf(keep_min, r0 <= v_at ? INFINITY : r0), fminf(r1 <= v_at ? INFINITY : r1, fminf(r2 <= v_at ? INFINITY : r2, r3 <= v_at ? INFINITY : r3)));
+                FSTAMP(8);
+                if (!(b0 | b1 | b2 | b3)) continue;
+                depart(top, b0);
+                if (b1) depart(top - 1, b1);
+                if (b2) depart(top - 2, b2);
+                if (b3) depart(top - 3, b3);
+            }
+            for (; top >= 0; --top) {
+                const float r = rr[top * kWave + lane];
+                const uint64_t b = __ballot(r <= v_at);
+                keep_min = fminf(keep_min, r <= v_at ? INFINITY : r);
+                FSTAMP(8);
+                if (b) depart(top, b);
+            }
+        } else
+        for (; top >= 0; top -= 4) {
             const float r0 = rr[top * kWave + lane], r1 = rr[max(top - 1, 0) * kWave + lane];
             const float r2 = rr[max(top - 2, 0) * kWave + lane], r3 = rr[max(top - 3, 0) * kWave + lane];   // unused entries hold +inf
             const uint64_t b0 = __ballot(r0 <= v_at), b1 = top >= 1 ? __ballot(r1 <= v_at) : 0ull;

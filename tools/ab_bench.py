@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Interleaved A/B timing of several builds of libongym_hip.so (one subprocess per build per round).
 
-    python tools/ab_bench.py [--rounds 3] [--batch 65536] [--steps 250] libA.so libB.so ...
+    python tools/ab_bench.py [--rounds 3] [--batch 65536] [--steps 250] [--per-round] [--per-quarter] libA.so libB.so ...
 Prints per-build kernel ms per launch (min / median) and env-steps/s. Device time from HIP events only."""
 import argparse
 import json
@@ -39,9 +39,12 @@ ap.add_argument("--warm", type=int, default=1000)
 ap.add_argument("--workload", default="nsfnet320")
 ap.add_argument("--capacity", type=int, default=0)
 ap.add_argument("--per-round", action="store_true", help="also print every round's median (the spread of a build against itself)")
+ap.add_argument("--per-quarter", action="store_true",
+                help="also print the median launch time by launch index modulo 4 (with --warm 1000 --steps 250: the quarter of an episode)")
 a = ap.parse_args()
 res = {l: [] for l in a.libs}
 rounds = {l: [] for l in a.libs}
+quarters = {l: [[], [], [], []] for l in a.libs}
 check = {}
 for rd in range(a.rounds):
     for lib in a.libs:
@@ -53,6 +56,8 @@ for rd in range(a.rounds):
         r = json.loads(out.stdout.strip().splitlines()[-1])
         res[lib] += r["ms"]; check[lib] = (r["acc"], r["steps"])
         rounds[lib].append(sorted(r["ms"])[len(r["ms"]) // 2])
+        for i, m in enumerate(r["ms"]):
+            quarters[lib][i % 4].append(m)
 for lib in a.libs:
     ms = sorted(res[lib])
     if not ms:
@@ -62,3 +67,5 @@ for lib in a.libs:
     print(f"{os.path.basename(lib):40s} min {ms[0]:8.2f} ms  med {med:8.2f} ms  mean {mean:8.3f} ms -> {a.batch * a.steps / mean * 1e3:.4e} steps/s   accepted/steps {check[lib]}")
     if a.per_round:
         print(f"{'':40s} round medians " + " ".join(f"{m:.3f}" for m in rounds[lib]) + f"  spread {max(rounds[lib]) - min(rounds[lib]):.3f} ms")
+    if a.per_quarter:
+        print(f"{'':40s} launch index mod 4 medians " + " ".join(f"{sorted(q)[len(q) // 2]:.3f}" for q in quarters[lib] if q))
