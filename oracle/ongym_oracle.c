@@ -132,6 +132,8 @@ void orc_destroy(orc_env *e) {
 void orc_seed(orc_env *e, uint64_t seed, uint64_t replica) {
     e->mode = 1; e->key = ongym_stream_key(seed, replica); e->req_index = 0;
 }
+/* the replica's margin from here on (the device's fork / load with ONGYM_STATE_KEEP_PARAMS: a state under other parameters) */
+void orc_set_margin(orc_env *e, double margin) { e->margin = margin; }
 void orc_set_trace(orc_env *e, const ongym_request *reqs, int64_t n) {
     e->mode = 2; e->trace = reqs; e->trace_n = n; e->trace_pos = 0;
 }

@@ -40,6 +40,8 @@ def lib():
         L.orc_destroy.argtypes = [vp]
         L.orc_seed.argtypes = [vp, C.c_uint64, C.c_uint64]
         L.orc_set_trace.argtypes = [vp, vp, C.c_int64]
+        L.orc_set_margin.argtypes = [vp, C.c_double]
+        L.orc_set_margin.restype = None
         L.orc_reset.argtypes = [vp]
         L.orc_reset_counters.argtypes = [vp]
         L.orc_reset_counters.restype = None
@@ -93,6 +95,10 @@ class OracleEnv:
     def set_trace(self, reqs: np.ndarray):
         self._trace = np.ascontiguousarray(reqs, REQUEST_DTYPE)
         self.L.orc_set_trace(self.h, self._trace.ctypes.data, len(self._trace))
+
+    def set_margin(self, margin: float):
+        """The margin of every decision from here on (the state stays): what fork(keep_params=True) gives a device replica."""
+        self.L.orc_set_margin(self.h, float(margin))
 
     def reset(self):
         return self.L.orc_reset(self.h)
