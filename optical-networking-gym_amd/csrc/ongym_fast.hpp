@@ -441,6 +441,27 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
     const uint32_t t_pk = t_n >= 1 ? (uint32_t)t_n | ((uint32_t)(lane & 7) << 11) | ((uint32_t)(t_n - 1) << 14) : 0u;
     // the tables the policy's search uses
     constexpr bool kLF = POL == ONGYM_POLICY_LOWEST_FRAGMENTATION;
+    // FIRST_FIT decides a whole run of formats from one evaluation (eval_one).  A run of lane q = 8 bi + m is the maximal
+    // stretch of consecutive format indices of bit rate bi around m whose slot count equals q's and is usable; which formats
+    // share a width never changes during a launch, so the run is tabulated here, as an 8-bit mask over the format index, and
+    // kept above the slot count in the same register (t_nr = n | run << 16: no further VGPR).  Every lane's run holds the
+    // lane's own bit, usable or not, and no bit at or above M (those lanes are not usable): the format loop strips a run from
+    // the feasible set, so it always strips the format it is at.
+    constexpr bool kRuns = POL == ONGYM_POLICY_FIRST_FIT;
+    uint32_t t_nr = (uint32_t)t_n;
+    if (kRuns) {
+        const int qm = lane & 7;
+        const bool usable = t_lim_hi > 0.0;
+        // the formats of the lane's bit rate with the lane's slot count (entries at or above M hold 0, which is not usable).
+        // Lane-local on purpose: the neighbours' counts through ds_bpermute and a ballot cost the prologue 13 to 28 VGPRs.
+        uint32_t same = 0;
+        if (usable)
+            for (int m = 0; m < kMaxMods; m++) same |= (uint32_t)(G(P.nreq_tab)[(lane & ~7) + m] == t_n) << m;
+        // the run: the set bits of `same` directly above m, and those from m downwards
+        const int hi = qm + __builtin_ctz(~(same >> (qm + 1))), lo = qm + 1 - __builtin_clz(~(same << (31 - qm)));
+        const uint32_t run = usable ? ((2u << hi) - 1u) & ~((1u << lo) - 1u) : 1u << qm;
+        t_nr |= run << 16;
+    }
     const int &w_n = kLF ? t1_n : t_n;
     const double &w_nlic = kLF ? t1_nlic : t_nlic, &w_selfa = kLF ? t1_selfa : t_selfa;
     const double &w_lim_lo = kLF ? t1_lim_lo : t_lim_lo, &w_lim_hi = kLF ? t1_lim_hi : t_lim_hi;
@@ -1046,15 +1067,22 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
             // pass 2: 1/GSNR of ONE candidate (start `first`, width nn) with lanes over the interferers.  Every lane finishes the
             // evaluation for ITS (bit rate, format) entry of the per-lane tables l_*; lane q is the one the walk is at.
             // The sum depends on the centre 2 first + nn alone, and first fit's start on nn alone: every format of width nn that
-            // the walk would visit next (`rest`: the feasible formats below q's, as bits of the modulation index) would be
-            // evaluated at the same start with the same sum, and its lane already holds its own exact decision.  So the formats
-            // of width nn that follow q in the walk, up to the first feasible format of another width (FIRST_FIT and
-            // LOAD_BALANCING; `rest` = 0 decides lane q alone), are decided here too, in walk order, and counted as the serial
-            // walk counts them: one evaluation each, up to the one that passes.  Returns the lane of the format that passes, or
-            // -1 (`rest` then loses the formats decided); ev_acc (and ev_ase / ev_nli when records are written) hold its values.
+            // the walk would visit next would be evaluated at the same start with the same sum, and its lane already holds its
+            // own exact decision.  So several formats are decided here, in walk order, and counted as the serial walk counts
+            // them: one evaluation each, up to the one that passes.  Which formats:
+            //  - FIRST_FIT (kRuns): the lanes of `grp`, the feasible formats of q's run of width nn (run table t_nr), which the
+            //    format loop has already taken out of the walk; q is the highest of them, and `rest` is not used.  A width
+            //    that recurs after an infeasible format of another width is a second run and a second evaluation with the
+            //    same start, sum and decisions; the counters count formats walked, so they agree as well.
+            //  - LOAD_BALANCING: the group is derived here from `rest`, the feasible formats below q's as bits of the
+            //    modulation index: those of width nn up to the first feasible format of another width; `rest` loses the formats
+            //    decided when none passes.  (With the run table its 5-wave kernels that write records spill more vector
+            //    registers, so it keeps this rule.)  `rest` = 0 decides lane q alone (LOWEST_FRAGMENTATION).
+            // Returns the lane of the format that passes, or -1; ev_acc (and ev_ase / ev_nli when records are written) hold its
+            // values.
             // `t`: the cached interferers' table values at this centre (gather(), or build_cache() for the evaluation after a build).
-            auto eval_one = [&](int first, int nn, int q, uint32_t &rest, const PathRec &pr, double l_a, double l_b, double l_d,
-                                double l_nlic, double l_lo, double l_hi, const TabPair (&t)[ENT]) -> int {
+            auto eval_one = [&](int first, int nn, int q, uint32_t &rest, uint64_t grp, const PathRec &pr, double l_a, double l_b,
+                                double l_d, double l_nlic, double l_lo, double l_hi, const TabPair (&t)[ENT]) -> int {
                 const uint32_t c2 = (uint32_t)(2 * first + nn);
                 double part = 0.0;
     #pragma unroll              // (a group without interferers has zero weights and zero table values: no select needed)
@@ -1075,30 +1103,48 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                 const double g_nli = fma(l_nlic, tot, l_d);
                 const double g_ase = fma(l_b, (double)first, l_a);                  // envs/qrmsa.pyx:901-905, see lane_fac
                 const double acc = g_ase + g_nli;
-                int ln = q, walked = 1;
-                const uint64_t yes = __ballot(acc <= l_lo);
-                if (!((yes >> q) & 1ull)) {
-                    uint64_t grp = 1ull << q;
-                    if (rest) {     // the walk's next formats of width nn, up to the first of another width
-                        const uint32_t same = (uint32_t)(__ballot(w_n == nn) >> (8 * cur_bi)) & rest, other = rest & ~same;
-                        const uint32_t g = other ? same & (~0u << (32 - __builtin_clz(other))) : same;
-                        grp |= (uint64_t)g << (8 * cur_bi);
+                if (!kRuns) {
+                    int ln = q, walked = 1;
+                    const uint64_t yes = __ballot(acc <= l_lo);
+                    if (!((yes >> q) & 1ull)) {
+                        uint64_t grp = 1ull << q;
+                        if (rest) {     // the walk's next formats of width nn, up to the first of another width
+                            const uint32_t same = (uint32_t)(__ballot(w_n == nn) >> (8 * cur_bi)) & rest, other = rest & ~same;
+                            const uint32_t g = other ? same & (~0u << (32 - __builtin_clz(other))) : same;
+                            grp |= (uint64_t)g << (8 * cur_bi);
+                        }
+                        // inside the 1e-9 band: the reference's own dB-domain expression (see qot_ok)
+                        const uint64_t band = grp & ~(yes | __ballot(acc >= l_hi));
+                        uint64_t pass = grp & yes;
+                        if (band) pass |= band & __ballot(10.0 * log10(1.0 / acc) >= P.mod_thr[lane & 7] + *KC(&ge->margin));
+                        ln = pass ? 63 - __builtin_clzll(pass) : -1;                  // the highest format first
+                        walked = __popcll(pass ? grp >> ln : grp);
+                        if (!pass) rest &= ~(uint32_t)(grp >> (8 * cur_bi));
                     }
-                    // inside the 1e-9 band: the reference's own dB-domain expression (see qot_ok)
-                    const uint64_t band = grp & ~(yes | __ballot(acc >= l_hi));
-                    uint64_t pass = grp & yes;
-                    if (band) pass |= band & __ballot(10.0 * log10(1.0 / acc) >= P.mod_thr[lane & 7] + *KC(&ge->margin));
-                    ln = pass ? 63 - __builtin_clzll(pass) : -1;                  // the highest format first
-                    walked = __popcll(pass ? grp >> ln : grp);
-                    if (!pass) rest &= ~(uint32_t)(grp >> (8 * cur_bi));
+                    d_evals += walked;
+                    lane_terms += e_terms + x_terms;
+                    if (walked > 1) lane_terms += (walked - 1) * (e_terms + x_terms);
+                    if (ln >= 0) {
+                        ev_acc = readlane_f64(acc, ln);
+                        if (REC) { ev_ase = readlane_f64(g_ase, ln); ev_nli = readlane_f64(g_nli, ln); }
+                    }
+                    return ln;
                 }
-                d_evals += walked;
-                lane_terms += e_terms + x_terms;
-                if (walked > 1) lane_terms += (walked - 1) * (e_terms + x_terms);
-                if (ln >= 0) {
+                // clearly passing, and not clearly failing: their difference is the 1e-9 band, where the reference's own dB-domain
+                // expression decides (see qot_ok).  l_lo < l_hi on every lane of a group, so `pass` lies inside `open`; the
+                // highest passing lane is taken whichever of the two tests let it pass, as the walk would.
+                uint64_t pass = __ballot(acc <= l_lo) & grp;
+                const uint64_t open = __ballot(acc < l_hi) & grp, band = open & ~pass;
+                if (band) pass |= band & __ballot(10.0 * log10(1.0 / acc) >= P.mod_thr[lane & 7] + *KC(&ge->margin));
+                int ln = -1, walked;
+                if (pass) {
+                    ln = 63 - __builtin_clzll(pass);                              // the highest format first
+                    walked = __popcll(grp >> ln);
                     ev_acc = readlane_f64(acc, ln);
                     if (REC) { ev_ase = readlane_f64(g_ase, ln); ev_nli = readlane_f64(g_nli, ln); }
-                }
+                } else walked = __popcll(grp);
+                d_evals += walked;
+                lane_terms = (int)(__umul24((uint32_t)(e_terms + x_terms), (uint32_t)walked) + (uint32_t)lane_terms);     // both factors far below 2^24
                 return ln;
             };
             // HIGHEST_SNR / LOWEST_FRAGMENTATION: the set bits of `v` (run-AND words, lane w = word w) as ascending slot indices in
@@ -1246,9 +1292,13 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
 #define FORMATS_DONE { asm volatile("s_mov_b32 %0, 0" : "=s"(feas)); continue; }
             do {
                 const int m = 31 - __builtin_clz(feas);            // best modulation first
-                asm("s_bitset0_b32 %0, %1" : "+s"(feas) : "s"(m));
                 const int q = 8 * cur_bi + m;
-                const int n = (int)rl((uint32_t)t_n, q);
+                const uint32_t nr = rl(t_nr, q);            // the slot count and, above it, the run of formats that share it
+                const int n = (int)(kRuns ? nr & 0xFFFFu : nr);
+                // the feasible formats of q's run leave the set together (the run always holds bit m): one evaluation decides them
+                uint32_t grp8 = 0;
+                if (kRuns) { grp8 = (nr >> 16) & feas; feas &= ~grp8; }
+                else asm("s_bitset0_b32 %0, %1" : "+s"(feas) : "s"(m));
                 const int nn = POL == ONGYM_POLICY_LOWEST_FRAGMENTATION ? n + 1 : n;      // quirk: the request is sized slots + 1 (:357)
                 if (nn + 1 < r_len) { runs = path_and(pmask); r_len = 1; }     // slot counts normally grow as the modulation index falls
                 runs = run_and32<WIDE>(runs, r_len, nn + 1);
@@ -1271,8 +1321,8 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                     continue;
                 }
                 uint32_t none = 0;
-                const int ln = eval_one(first, nn, q, POL == ONGYM_POLICY_LOWEST_FRAGMENTATION ? none : feas, pr, r_a, r_b, r_d, w_nlic,
-                                        w_lim_lo, w_lim_hi, tv);
+                const int ln = eval_one(first, nn, q, POL == ONGYM_POLICY_LOWEST_FRAGMENTATION ? none : feas,
+                                        (uint64_t)grp8 << (8 * cur_bi), pr, r_a, r_b, r_d, w_nlic, w_lim_lo, w_lim_hi, tv);
                 FSTAMP(5);
                 if (ln >= 0) {          // all formats of the group have n slots
                     ch_k = k; ch_m = ln & 7; ch_slot = first; ch_n = n; ch_path = path;
@@ -1299,7 +1349,7 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                 uint32_t none = 0;
                 TabPair tv[ENT];
                 gather((uint32_t)(2 * ch_slot + ch_n), tv);
-                if (eval_one(ch_slot, ch_n, 8 * cur_bi + ch_m, none, pr, sf.c1 * pr.ase, sf.cb * pr.ase, sf.c2 * pr.w1, t_nlic, t_lim_lo,
+                if (eval_one(ch_slot, ch_n, 8 * cur_bi + ch_m, none, 0, pr, sf.c1 * pr.ase, sf.cb * pr.ase, sf.c2 * pr.w1, t_nlic, t_lim_lo,
                              t_lim_hi, tv) >= 0) {
                     ch_acc = ev_acc; ch_ase = ev_ase; ch_nli = ev_nli;
                 } else { ch_k = -1; lf_qot = true; }
@@ -1347,7 +1397,7 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                 // smallest slot count.
                 int n_small = 0x7fffffff;
                 for (int m = M - 1; m >= 0; m--) {
-                    const int n = (int)rl((uint32_t)t_n, 8 * cur_bi + m);
+                    const int n = (int)(rl(t_nr, 8 * cur_bi + m) & (kRuns ? 0xFFFFu : ~0u));
                     if (n > 0) n_small = min(n_small, n);
                 }
                 if (POL == ONGYM_POLICY_LOWEST_FRAGMENTATION) n_small += 1;
@@ -1369,7 +1419,7 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                 int bres = 0, bosnr = 0;
                 int n_small = 0x7fffffff, n_big = 0, n_last = 0;
                 for (int m = M - 1; m >= 0; m--) {
-                    const int n = (int)rl((uint32_t)t_n, 8 * cur_bi + m);
+                    const int n = (int)(rl(t_nr, 8 * cur_bi + m) & (kRuns ? 0xFFFFu : ~0u));
                     if (n <= 0) continue;
                     n_small = min(n_small, n); n_big = max(n_big, n); n_last = n;
                 }
