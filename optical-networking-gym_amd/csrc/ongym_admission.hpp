@@ -177,7 +177,7 @@ __global__ __launch_bounds__(64) void k_admission_map(const Params *__restrict__
                         const double fc = P.f0 + (P.slot_bw * first) + (P.slot_bw * (nn / 2.0));
                         double lb = (bw * fc * p.ase) * c.rp[0];
                         if (UA) lb += kf.nlic * (p.w1 * kf.selfa);
-                        if (uniform_i32(lb >= c.lim[mm] * (1.0 + 1e-9))) { refused |= 1u << r; continue; }
+                        if (uniform_i32(lb >= c.lim[mm] * (1.0 + kQotBand))) { refused |= 1u << r; continue; }
                     }
                     if (L < 0) L = gn_build_list<R32>(c, p.m0, p.m1);
                     const GnLin g = gn_eval<UA, R32>(c, p, L, first, nn, kf);

@@ -146,7 +146,7 @@ __device__ __forceinline__ void observe_blocks_env(Ctx &c, int J, uint64_t *row,
                         const double fc = P.f0 + (P.slot_bw * a) + (P.slot_bw * (n / 2.0));
                         double lb = (bw * fc * p.ase) * c.rp[0];
                         if (UNIFORM_ALPHA) lb += c.nlic[m] * (p.w1 * c.selfa[m]);
-                        if (uniform_i32(lb >= c.lim[m] * (1.0 + 1e-9))) continue;
+                        if (uniform_i32(lb >= c.lim[m] * (1.0 + kQotBand))) continue;
                     }
                     if (L < 0) L = gn_build_list<R32>(c, p.m0, p.m1);
                     g = gn_eval<UNIFORM_ALPHA, R32>(c, p, L, a, n, coef_for_mod(c, m));

@@ -660,14 +660,25 @@ __device__ __forceinline__ void gn_to_db(const GnLin &g, double out[3]) {   // c
     out[2] = -10.0 * log10(g.nli);
 }
 
-// GSNR >= minimum_osnr + margin ?  (heuristics.py:957-958, envs/qrmsa.pyx:911). The comparison is made in the linear
-// domain against lim = 10^(-(thr+margin)/10); inside a 1e-9 relative band around the limit it falls back to the
-// reference's own expression 10*log10(1/acc) >= thr + margin, so the decision is the dB-domain one everywhere.
+// ---- the admission rule: GSNR >= threshold (+ margin), decided on the linear 1/GSNR.  kQotBand is the relative half-width of
+// the band around the limit in which the reference's dB expression decides; every text of the rule outside k_fast is written on it.
+constexpr double kQotBand = 1e-9;
+
+// 1/GSNR `acc` against lim = 10^(-thr_db/10); inside the band the reference's 10 log10(1/acc) >= thr_db
+// (heuristics.py:957-958, envs/qrmsa.pyx:911), so the decision is the dB-domain one everywhere.  A value per lane.
+__device__ __forceinline__ bool qot_pass(double acc, double lim, double thr_db) {
+    if (acc <= lim * (1.0 - kQotBand)) return true;
+    if (acc >= lim * (1.0 + kQotBand)) return false;
+    return 10.0 * log10(1.0 / acc) >= thr_db;
+}
+
+// GSNR >= minimum_osnr + margin of modulation m ?  Wave-uniform.  qot_pass' decision in a text of its own, which adds the margin
+// only inside the band (DESIGN section 18 has what calling qot_pass here did to the kernels).
 __device__ __forceinline__ int qot_ok(const Ctx &c, const GnLin &g, int m, double margin) {
     double acc = g.ase + g.nli, lim = c.lim[m];
     int ok;
-    if (acc <= lim * (1.0 - 1e-9)) ok = 1;
-    else if (acc >= lim * (1.0 + 1e-9)) ok = 0;
+    if (acc <= lim * (1.0 - kQotBand)) ok = 1;
+    else if (acc >= lim * (1.0 + kQotBand)) ok = 0;
     else ok = 10.0 * log10(1.0 / acc) >= c.P.mod_thr[m] + margin;
     return uniform_i32(ok);
 }
@@ -716,12 +727,12 @@ __device__ __forceinline__ void policy_first_fit(Ctx &c, int src, int dst, doubl
                 // No interferer term of the NLI sum is negative (checked at create), so
                 //   1/SNR >= 1/SNR_ase + 1/SNR_nli(self-channel term only):
                 // a candidate that fails on this O(1) bound fails the full evaluation too (same expressions as
-                // gn_eval, same 1e-9 guard band as qot_ok).
+                // gn_eval, same guard band kQotBand as qot_ok).
                 double bw = P.slot_bw * n;
                 double fc = P.f0 + (P.slot_bw * first) + (P.slot_bw * (n / 2.0));
                 double lb = (bw * fc * p.ase) * c.rp[0];
                 if (UNIFORM_ALPHA) lb += c.nlic[m] * (p.w1 * c.selfa[m]);
-                if (uniform_i32(lb >= c.lim[m] * (1.0 + 1e-9))) { bosnr = 1; bres = 0; c.gn_skips++; continue; }
+                if (uniform_i32(lb >= c.lim[m] * (1.0 + kQotBand))) { bosnr = 1; bres = 0; c.gn_skips++; continue; }
             }
             if (L < 0) { L = gn_build_list<R32>(c, p.m0, p.m1); STAMP(c, 3); }
             GnLin g = gn_eval<UNIFORM_ALPHA, R32>(c, p, L, first, n, coef_for_mod(c, m));
@@ -785,7 +796,7 @@ __device__ __forceinline__ void policy_load_balancing(Ctx &c, int src, int dst, 
                 double fc = P.f0 + (P.slot_bw * first) + (P.slot_bw * (n / 2.0));
                 double lb = (bw * fc * p.ase) * c.rp[0];
                 if (UNIFORM_ALPHA) lb += c.nlic[m] * (p.w1 * c.selfa[m]);
-                if (uniform_i32(lb >= c.lim[m] * (1.0 + 1e-9))) { any_osnr = 1; c.gn_skips++; continue; }
+                if (uniform_i32(lb >= c.lim[m] * (1.0 + kQotBand))) { any_osnr = 1; c.gn_skips++; continue; }
             }
             if (L < 0) L = gn_build_list<R32>(c, p.m0, p.m1);
             GnLin g = gn_eval<UNIFORM_ALPHA, R32>(c, p, L, first, n, coef_for_mod(c, m));
@@ -1267,12 +1278,13 @@ __device__ __forceinline__ GnLin gn_service_acc(Ctx &c, int iy, int py, int sy, 
     return g;
 }
 
-// GSNR < minimum_osnr of modulation `my` (no margin)?  Linear-domain compare with the dB fallback band of qot_ok.
+// GSNR < minimum_osnr of modulation `my` (no margin)?  Wave-uniform.  The negation of qot_pass(acc, lim0[my], mod_thr[my]) for
+// the finite values that reach it, in a text of its own with the failing compare first.
 __device__ __forceinline__ int below_minimum_osnr(const Ctx &c, double acc, int my) {
     const double lim = c.lim0[my];
     int below;
-    if (acc >= lim * (1.0 + 1e-9)) below = 1;
-    else if (acc <= lim * (1.0 - 1e-9)) below = 0;
+    if (acc >= lim * (1.0 + kQotBand)) below = 1;
+    else if (acc <= lim * (1.0 - kQotBand)) below = 0;
     else below = 10.0 * log10(1.0 / acc) < c.P.mod_thr[my];
     return uniform_i32(below);
 }
@@ -1845,8 +1857,7 @@ __device__ __forceinline__ void observe_env(Ctx &c, double *Fx, uint64_t *Vw, ui
                     if (((w >> c.lane) & 1ull) && s0 < S) {
                         const double fc = P.f0 + (P.slot_bw * s0) + (P.slot_bw * (n / 2.0));
                         const double acc = (bw * fc * pase) * c.rp[0] + nlic * (self + Fx[2 * s0 + n]);
-                        if (acc <= lim * (1.0 - 1e-9)) pass = true;                       // same decision as qot_ok
-                        else if (acc < lim * (1.0 + 1e-9)) pass |= 10.0 * log10(1.0 / acc) >= P.mod_thr[m] + e->margin;
+                        pass |= qot_pass(acc, lim, P.mod_thr[m] + e->margin);
                     }
                 }
                 if (__ballot(pass)) { max_idx = max(m, M - 1); found = true; }
@@ -2022,16 +2033,13 @@ __device__ __forceinline__ void policy_highest_snr(Ctx &c, int src, int dst, dou
                     const double fc = P.f0 + (P.slot_bw * s) + (P.slot_bw * (n / 2.0));
                     const double acc = (bw * fc * pase) * c.rp[0] + nlic * (self + c.fl.Fx[2 * s + n]);
                     const double osnr = -10.0 * log10(acc);
-                    bool ok;
-                    if (acc <= lim * (1.0 - 1e-9)) ok = true;
-                    else if (acc >= lim * (1.0 + 1e-9)) ok = false;
-                    else ok = 10.0 * log10(1.0 / acc) >= thr;
-                    if (ok) v = osnr; else fail = true;
+                    if (qot_pass(acc, lim, thr)) v = osnr; else fail = true;
                 }
                 if (__ballot(fail)) any_osnr = 1;
                 const double vmax = wave_max_f64(v);
-                if (vmax > best_osnr + 1e-9) {                            // strict, beyond the rounding noise (exact ties of the reference: equal routes
-                                                                          // on an empty network; see eval_cands in ongym_fast.hpp): the first maximum wins
+                if (vmax > best_osnr + 1e-9) {                            // tie noise in dB, not kQotBand: strict, beyond the rounding noise (exact ties of
+                                                                          // the reference: equal routes on an empty network; see eval_cands in
+                                                                          // ongym_fast.hpp): the first maximum wins
                     const uint64_t bal = __ballot(v == vmax);
                     const int ln = __ffsll((unsigned long long)bal) - 1;
                     best_osnr = vmax;

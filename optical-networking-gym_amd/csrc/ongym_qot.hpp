@@ -30,10 +30,10 @@ __host__ __device__ inline size_t qot_lds_bytes(const Params &P) {
 }
 
 // below_minimum_osnr / qot_ok for a value per lane (theirs make the decision wave-uniform): 1/GSNR `acc` against the linear limit
-// `lim` = 10^(-thr_db/10), inside the 1e-9 band the reference's dB expression 10 log10(1/acc) < thr_db
+// `lim` = 10^(-thr_db/10), inside the band kQotBand the reference's dB expression 10 log10(1/acc) < thr_db
 __device__ __forceinline__ bool below_lane(double acc, double lim, double thr_db) {
-    if (acc >= lim * (1.0 + 1e-9)) return true;
-    if (acc <= lim * (1.0 - 1e-9)) return false;
+    if (acc >= lim * (1.0 + kQotBand)) return true;
+    if (acc <= lim * (1.0 - kQotBand)) return false;
     return 10.0 * log10(1.0 / acc) < thr_db;
 }
 

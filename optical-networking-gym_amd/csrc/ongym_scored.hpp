@@ -170,7 +170,7 @@ __device__ __forceinline__ void policy_scored(Ctx &c, int policy, int src, int d
                     // only grows with the slot index, so every later start of this format fails too
                     const double bw = P.slot_bw * n, fc = P.f0 + (P.slot_bw * s0) + (P.slot_bw * (n / 2.0));
                     const double lb = (bw * fc * p.ase) * c.rp[0] + c.nlic[m] * (p.w1 * c.selfa[m]);
-                    if (uniform_i32(lb >= c.lim[m] * (1.0 + 1e-9))) { bosnr = 1; c.gn_skips++; break; }
+                    if (uniform_i32(lb >= c.lim[m] * (1.0 + kQotBand))) { bosnr = 1; c.gn_skips++; break; }
                 }
                 if (L < 0) L = gn_build_list<R32>(c, p.m0, p.m1);
                 const GnLin g = gn_eval<UNIFORM_ALPHA, R32>(c, p, L, s0, n, coef_for_mod(c, m));
