@@ -590,13 +590,24 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
         cnt += (lane == 16 + cur_bi) ? 1 : 0;           // bit_rate_requested, by bit rate
     };
 
+    // First fit without step records ("First route"): the walk over the routes is entered with the route id
+    // that came with the request (kFrRoute0), a request is provisioned where its format passes (kFrInPlace), path_and enters its
+    // pair loop without a test, and with one mask word a departure tests its link against the lane's own bit (kFrLaneBit).  The
+    // kernels that write records keep the plain forms: with these their 5-wave instantiations spill more vector registers.  The
+    // other policies keep them too, and with them the parent's registers.
+    constexpr bool kFrRoute0 = POL == ONGYM_POLICY_FIRST_FIT && !REC, kFrInPlace = kFrRoute0;
+    constexpr bool kFrPathAnd = kFrRoute0, kFrLaneBit = kFrRoute0 && !M64;
+    uint32_t lane_bit = lane < 32 ? 1u << lane : 0u;        // defined once per launch; pinned, or the shift comes back at every use
+    if (kFrLaneBit) asm volatile("" : "+v"(lane_bit));
+
     // AND of the free bitmaps of a path's links, extended by the virtual free slot S (see path_free_ext); the links come
     // from the path's mask (their order does not matter)
     auto path_and = [&](uint64_t links64) -> uint32_t {
         const int wl = min(lane, RW - 1);
         uint32_t x = lane < RW ? ~0u : 0u;
         // Two links per trip while two remain: both rows are read before either is used, so a pair costs one LDS round trip
-        // (the same instructions per link; no neutral read pads an odd count).
+        // (the same instructions per link; no neutral read pads an odd count).  kFrPathAnd: every caller passes the mask of a real
+        // route (hops >= 1), so the loop is entered without testing `links` first.
         auto row = [](uint32_t a) -> uint32_t { return *(const __attribute__((address_space(3))) uint32_t *)(uintptr_t)a; };
         if (M64) {
             uint64_t links = links64;
@@ -606,11 +617,12 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                 asm("s_bitset0_b64 %0, %1" : "+s"(links) : "s"(l));
                 return __umul24((uint32_t)l, v_rw4) + v_word;
             };
-            while (links) {
-                const uint32_t r0 = row(take());
-                if (links) x &= row(take());
-                x &= r0;
-            }
+            if (kFrPathAnd || links)
+                do {
+                    const uint32_t r0 = row(take());
+                    if (links) x &= row(take());
+                    x &= r0;
+                } while (links);
         } else {
             // per link: s_ff1, s_bitset0 (one instruction instead of the add/and pair of links &= links - 1), and the row address
             // lane offset + l * row bytes as one v_mad_u32_u24 on the vector pipe
@@ -621,11 +633,12 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                 asm("s_bitset0_b32 %0, %1" : "+s"(links) : "s"(l));
                 return __umul24((uint32_t)l, v_rw4) + v_word;
             };
-            while (links) {
-                const uint32_t r0 = row(take());
-                if (links) x &= row(take());
-                x &= r0;
-            }
+            if (kFrPathAnd || links)
+                do {
+                    const uint32_t r0 = row(take());
+                    if (links) x &= row(take());
+                    x &= r0;
+                } while (links);
         }
         if (lane == (S >> 5)) x |= 1u << (S & 31);
         return x;
@@ -655,10 +668,13 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
     };
 
     // the same for slots [lo, lo+len), len <= 33, with `lo` and `len` living in VGPRs (wave-uniform values): two words per link,
-    // EXEC from the link mask held in a VGPR pair (departures) — no scalar arithmetic at all
+    // EXEC from the link mask held in a VGPR pair (departures) — no scalar arithmetic at all.  kFrLaneBit: lanes 32 and up hold
+    // no link, so `lane < 32` is folded into the lane's bit (0 there): v_and + v_cmp, without the s_xor / s_and on the lane test
     auto mark_v = [&](uint32_t m_lo, uint32_t m_hi, uint32_t lo, uint32_t len, bool free_) {
         const uint64_t m = ((1ull << len) - 1ull) << (lo & 31u);
-        const bool mine = lane < 32 ? ((m_lo >> lane) & 1u) : (M64 && ((m_hi >> (lane - 32)) & 1u));
+        bool mine;
+        if constexpr (kFrLaneBit) mine = (m_lo & lane_bit) != 0;        // (discarded elsewhere: the other kernels' lambda does not capture lane_bit)
+        else mine = lane < 32 ? ((m_lo >> lane) & 1u) : (M64 && ((m_hi >> (lane - 32)) & 1u));
         if (mine) {
             uint32_t *w = occ + (uint32_t)lane * (uint32_t)RW + (lo >> 5);          // lane l = link l: its row
             if (free_) { __hip_atomic_fetch_or(w, (uint32_t)m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
@@ -866,10 +882,44 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
             FSTAMP(13);
         }
 
-        for (int r = 0; r < nk; r++) {
+        // _provision_path (:1288-1325) of the chosen candidate: format c_m (c_n slots, + one guard slot unless the allocation ends at
+        // S) from c_slot on route c_path (link mask c_mask), 1/GSNR c_acc.  Record word b (fast_pack_b / fast_pack_b64): the format's
+        // part (n | modulation << 11 | (n - 1) << 14) comes from the per-lane table, the rest is the start and the path id (or the
+        // mask's high bits); c_n == t_n of the chosen lane.  rel: float + float (:1329), compared as float32 (:1114-1115).  First fit
+        // without records expands it where the format passes (kFrInPlace), everything else after the search.  (A macro, not a lambda:
+        // a lambda that the other policies' kernels also hold moves their register allocation, DESIGN.md section 5, "First route".)
+#define ONGYM_PROVISION(c_m, c_slot, c_n, c_path, c_mask, c_acc) {                                                          \
+            int end = (c_slot) + (c_n); if (end < S) end += 1;                                                                  \
+            mark((c_mask), (c_slot), end, false);                                                                               \
+            if (POL == ONGYM_POLICY_LOWEST_FRAGMENTATION) ls_dirty |= (((c_mask) >> lane) & 1ull) != 0;                         \
+            const float rel = v_at + cur_ht;                                                                                    \
+            next_rel = fminf(next_rel, rel);                                                                                    \
+            const uint32_t ra = (uint32_t)(c_mask);                                                                             \
+            const uint32_t rb = rl(t_pk, 8 * cur_bi + (c_m)) + 2u * (uint32_t)(c_slot) +                                        \
+                                ((M64 ? (uint32_t)((c_mask) >> 32) : (uint32_t)((c_path) & 0x1FF)) << 23);                      \
+            const uint32_t v_act = vz + (uint32_t)active;                                                                       \
+            lds_write_lane0(rec_base + v_act * 8u, ra, rb, rr_base + v_act * 4u, __float_as_uint(rel));                         \
+            active++;                                                                                                           \
+            if (TRACE) d_acc++;                                                                                                 \
+            cnt += (lane == 8 + (c_m) || lane == 24 + cur_bi) ? 1 : 0;                                                          \
+            osnr_prod *= (c_acc);                                                                                               \
+            if (osnr_prod < 1e-250) { if (lane == 0) cold[4] += -10.0 * log10(osnr_prod); osnr_prod = 1.0; wave_sync(); }       \
+        }
+        bool chosen = false;                // kFrInPlace: a route served the request (or would have: the table is full)
+
+        // First fit without records (kFrRoute0) walks the routes from the id that came with the request: 96 % of the accepted
+        // requests are served by that first route, so the loop is entered with it (a pair without a route, cur_p0 < 0, tries
+        // nothing) and the next route's id is fetched only behind a route that failed.
+        int fr_path = cur_p0;
+        for (int r = 0; kFrRoute0 ? fr_path >= 0 : r < nk;
+             kFrRoute0 ? (void)(fr_path = ++r < K ? uniform_i32(KC(P.pair_paths)[pair_base() + r]) : -1) : (void)r++) {
             int k = r, path;
             PathRec pr;
-            if (POL == ONGYM_POLICY_FIRST_FIT) {
+            if (kFrRoute0) {
+                path = fr_path;
+                pr = load_path_rec(path_recs, path);
+                d_paths++; d_hops += pr.hops;
+            } else if (POL == ONGYM_POLICY_FIRST_FIT) {
                 path = k == 0 ? cur_p0 : uniform_i32(KC(P.pair_paths)[pair_base() + k]);
                 if (path < 0) break;
                 // (fetching the first route's record already when the request is popped was measured 2.4 % SLOWER: eight more
@@ -1325,9 +1375,18 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                                         (uint64_t)grp8 << (8 * cur_bi), pr, r_a, r_b, r_d, w_nlic, w_lim_lo, w_lim_hi, tv);
                 FSTAMP(5);
                 if (ln >= 0) {          // all formats of the group have n slots
-                    ch_k = k; ch_m = ln & 7; ch_slot = first; ch_n = n; ch_path = path;
-                    ch_mask = pmask;
-                    ch_acc = ev_acc; ch_ase = ev_ase; ch_nli = ev_nli;
+                    if constexpr (kFrInPlace) {
+                        // Accepted where the format passes: the candidate goes from the registers it was found in straight to the
+                        // provisioning code, and nothing is carried through the loop exits but `chosen` (no record is written here,
+                        // so ch_* are not needed).  The loop still has its one exit at the bottom.
+                        if (active >= C) { d_flags |= ONGYM_F_OVERFLOW; erej++; d_rej++; }    // the table is full: a rejection
+                        else ONGYM_PROVISION(ln & 7, first, n, path, pmask, ev_acc)
+                        chosen = true;
+                    } else {
+                        ch_k = k; ch_m = ln & 7; ch_slot = first; ch_n = n; ch_path = path;
+                        ch_mask = pmask;
+                        ch_acc = ev_acc; ch_ase = ev_ase; ch_nli = ev_nli;
+                    }
                     FORMATS_DONE;
                 }
                 if (POL == ONGYM_POLICY_LOWEST_FRAGMENTATION) {
@@ -1355,37 +1414,18 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                 } else { ch_k = -1; lf_qot = true; }
                 break;
             }
-            if (POL != ONGYM_POLICY_HIGHEST_SNR && ch_k >= 0) break;
+            if (kFrInPlace ? chosen : POL != ONGYM_POLICY_HIGHEST_SNR && ch_k >= 0) break;
         }
 
         // ================= step (envs/qrmsa.pyx:838-1065) ==============================================================
+        // (accepted in place: the request is provisioned, or its overflow counted, where the format passed; `chosen` says so, and
+        //  ch_k is still -1)
         int accepted = ch_k >= 0;
         int rflags = 0;
         if (accepted && active >= C) { accepted = 0; rflags |= ONGYM_F_OVERFLOW; d_flags |= ONGYM_F_OVERFLOW; }
         if (accepted) {
-            // _provision_path (:1288-1325): n slots + one guard slot unless the allocation ends at S
-            int end = ch_slot + ch_n; if (end < S) end += 1;
-#ifdef ONGYM_X_ACCEPT_MARKV
-            if (end - ch_slot <= 33) mark_v((uint32_t)ch_mask, M64 ? (uint32_t)(ch_mask >> 32) : 0u, (uint32_t)ch_slot + vz, (uint32_t)(end - ch_slot) + vz, false);
-            else
-#endif
-            mark(ch_mask, ch_slot, end, false);
-            if (POL == ONGYM_POLICY_LOWEST_FRAGMENTATION) ls_dirty |= ((ch_mask >> lane) & 1ull) != 0;      // these rows changed
-            const float rel = v_at + cur_ht;                  // float + float (:1329); compared as float32 (:1114-1115)
-            next_rel = fminf(next_rel, rel);
-            const uint32_t ra = (uint32_t)ch_mask;
-            // record word b (fast_pack_b / fast_pack_b64): the format's part (n | modulation << 11 | (n - 1) << 14) comes from the
-            // per-lane table, the rest is the start and the path id (or the mask's high bits); ch_n == t_n of the chosen lane
-            const uint32_t rb = rl(t_pk, 8 * cur_bi + ch_m) + 2u * (uint32_t)ch_slot +
-                                ((M64 ? (uint32_t)(ch_mask >> 32) : (uint32_t)(ch_path & 0x1FF)) << 23);
-            const uint32_t v_act = vz + (uint32_t)active;        // (address arithmetic on the vector pipe, see vz)
-            lds_write_lane0(rec_base + v_act * 8u, ra, rb, rr_base + v_act * 4u, __float_as_uint(rel));
-            active++;
-            if (TRACE) d_acc++;
-            cnt += (lane == 8 + ch_m || lane == 24 + cur_bi) ? 1 : 0;
-            osnr_prod *= ch_acc;
-            if (osnr_prod < 1e-250) { if (lane == 0) cold[4] += -10.0 * log10(osnr_prod); osnr_prod = 1.0; wave_sync(); }
-        } else {
+            ONGYM_PROVISION(ch_m, ch_slot, ch_n, ch_path, ch_mask, ch_acc)
+        } else if (!kFrInPlace || !chosen) {
             erej++; d_rej++;
             if (ch_k < 0 && POL == ONGYM_POLICY_LOWEST_FRAGMENTATION && lf_qot) {
                 rflags |= ONGYM_F_QOT_ERROR | ONGYM_F_BLOCKED_OSNR;
@@ -1632,6 +1672,7 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
         for (int i = 0; i < ONGYM_NSTAMPS; i++) atomicAdd(&P.dbg[i], stamp_acc[i]);
 #endif
 #undef FSTAMP
+#undef ONGYM_PROVISION
 }
 
 }  // namespace ongym
