@@ -37,7 +37,7 @@
 // The state in HBM is the generic kernels' (same arrays, same record codec), converted on load / store: every other entry
 // point keeps working on the same environment, and a launch may be split anywhere.
 //
-// Eligibility (checked on the host in build(), ongym_hip.hip; lean_unit() there decides per launch): policy-step mode,
+// Eligibility (checked on the host at create: build_lean(), ongym_hip.hip; lean_unit() there decides per launch): policy-step mode,
 // device request generator or a host trace whose bit rates all come from the configured table, discrete bit rates (<= 8,
 // integer-valued), uniform attenuation, ase_shortcut, no defragmentation / disruptions / id tracking,
 // modulations_to_consider == n_mods, n_links <= 32 + kM64HiBits = 41, n_nodes <= 64, every slot count of the traffic table

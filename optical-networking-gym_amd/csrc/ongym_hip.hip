@@ -19,7 +19,7 @@
 #include "ongym_device.hpp"
 #include "ongym_host.hpp"
 #include "ongym_fast.hpp"      // fast_lds_bytes, PathRec (the kernels themselves: ongym_fast.hip)
-#include "ongym_lwtab.hpp"     // shared-link weight table of the lean kernels, built at create
+#include "ongym_tables.hpp"    // config_check, derive_tables: the host half of create (with ongym_lwtab.hpp)
 #include "ongym_scored.hpp"
 #include "ongym_policy_head.hpp"   // masked categorical action head (ongym_masked_categorical)
 #include "ongym_gae.hpp"           // GAE over a rollout (ongym_gae)
@@ -378,7 +378,7 @@ static auto with_layout(const Params &P, F &&f) {
     });
 }
 
-// The lean units (ongym_fast.hip): the policies that have one, each with its narrow and its wide build.  build() prepares them
+// The lean units (ongym_fast.hip): the policies that have one, each with its narrow and its wide build.  prepare_lean() prepares them
 // in this order; without the first row (first fit) no lean kernel runs.
 struct LeanFns {
     int (*prepare)(ongym_env *);
@@ -548,359 +548,187 @@ static size_t admission_part_rows(const Params &P) {
 constexpr int kPlayoutByReplica = 0;
 
 // At the end of create, after every allocation of build(): the buffer of the groups' partial sums (so that no call allocates, and
-// the state arrays lie where they lay without it), and the measurement knob
+// the state arrays lie where they lay without it)
 static int admission_prepare(ongym_env *env) {
     Stage &st = env->stage[kStageAdmissionPart];
     const size_t bytes = admission_part_rows(env->P) * kAdmissionPart * sizeof(double);
     HIP_TRY(env, hipMalloc(&st.base, bytes));
     st.bytes = bytes;
+    return 0;
+}
+
+// The measurement knobs of create, read from the environment once: the three of the tables and the lean kernels (CreateKnobs),
+// and the two of the admission map and the playouts, which stay with the environment
+static CreateKnobs read_knobs(ongym_env *env) {
+    const auto flag = [](const char *name) { const char *v = std::getenv(name); return v && v[0] == '1'; };
+    CreateKnobs k;
+    k.force_generic = flag("ONGYM_FORCE_GENERIC");
+    k.force_wide = flag("ONGYM_FORCE_WIDE");
+    k.no_lwtab = flag("ONGYM_FAST_NO_LWTAB");
     const char *g = std::getenv("ONGYM_ADMISSION_GROUPS");
     env->admission_groups = g ? std::max(0, std::atoi(g)) : 0;
     const char *o = std::getenv("ONGYM_PLAYOUT_ORDER");
     env->playout_by_replica = o ? std::atoi(o) != 0 : kPlayoutByReplica;
-    return 0;
+    return k;
 }
 
-static int build(ongym_env *env, const ongym_config *c) {
+// ---- create: config_check and derive_tables (ongym_tables.hpp, no device needed), then the steps below in build()'s order.
+// The device allocations and copies keep one fixed sequence: where the state arrays lie is part of what gets timed. ----
+static_assert(kCfgMaxMods == kMaxMods && kCfgMaxLinks == kMaxLinks && kCfgMaxHops == kMaxHops, "ongym_tables.hpp checks other limits");
+
+// the scalar fields of Params and the per-format tables
+static void set_params(ongym_env *env, const ongym_config *c, const HostTables &T) {
     Params &P = env->P;
-    if (c->n_nodes <= 1 || c->n_links <= 0 || c->n_paths <= 0 || c->k_paths <= 0 || c->max_hops <= 0 ||
-        c->n_mods <= 0 || c->n_slots <= 0 || c->batch <= 0 || c->episode_length <= 1)
-        return fail_arg(env, "non-positive size in ongym_config");
-    if (c->n_mods > kMaxMods) return fail_arg(env, "n_mods > 8", ONGYM_E_LIMIT);
-    if (c->n_links > kMaxLinks) return fail_arg(env, "n_links > 128", ONGYM_E_LIMIT);
-    if (c->max_hops > kMaxHops) return fail_arg(env, "max_hops > 64", ONGYM_E_LIMIT);
-    if (c->n_slots > 1023) return fail_arg(env, "n_slots > 1023", ONGYM_E_LIMIT);
-    if (c->n_paths > 65535) return fail_arg(env, "n_paths > 65535", ONGYM_E_LIMIT);
-    if (c->capacity <= 0 || c->capacity % 64 || c->capacity > 65535)
-        return fail_arg(env, "capacity must be a multiple of 64 in (0, 65535)");
-    if (!c->pair_paths || !c->path_hops || !c->path_links || !c->link_nspans || !c->link_span_km || !c->link_alpha ||
-        !c->link_nf || !c->mod_se || !c->mod_min_osnr || !c->node_cum)
-        return fail_arg(env, "null table pointer in ongym_config");
-    if (c->bit_rate_mode == 0 && (!c->bit_rates || !c->bit_rate_cum || c->n_bit_rates <= 0))
-        return fail_arg(env, "discrete bit-rate mode needs bit_rates/bit_rate_cum");
-    if (c->load <= 0 || c->mean_holding_time <= 0) return fail_arg(env, "load and mean_holding_time must be positive");
-
-    const int N = c->n_nodes, E = c->n_links, NP = c->n_paths, K = c->k_paths, H = c->max_hops, M = c->n_mods;
-    // validate tables on the host before any kernel indexes with them
-    for (int i = 0; i < N * N * K; i++)
-        if (c->pair_paths[i] < -1 || c->pair_paths[i] >= NP) return fail_arg(env, "pair_paths entry out of range");
-    for (int p = 0; p < NP; p++) {
-        if (c->path_hops[p] <= 0 || c->path_hops[p] > H) return fail_arg(env, "path_hops entry out of range");
-        for (int h = 0; h < c->path_hops[p]; h++)
-            if (c->path_links[p * H + h] < 0 || c->path_links[p * H + h] >= E)
-                return fail_arg(env, "path_links entry out of range");
-    }
-    for (int m = 0; m < M; m++)
-        if (c->mod_se[m] < 1 || c->mod_se[m] > 6) return fail_arg(env, "spectral efficiency must be 1..6");
-    for (int e = 0; e < E; e++)
-        if (!(c->link_alpha[e] > 0) || !(c->link_span_km[e] > 0) || c->link_nspans[e] <= 0)
-            return fail_arg(env, "link span parameters must be positive");
-
-    P.n_nodes = N; P.n_links = E; P.n_paths = NP; P.k_paths = K; P.max_hops = H; P.n_mods = M; P.n_slots = c->n_slots;
+    const int M = c->n_mods;
+    P.n_nodes = c->n_nodes; P.n_links = c->n_links; P.n_paths = c->n_paths; P.k_paths = c->k_paths; P.max_hops = c->max_hops;
+    P.n_mods = M; P.n_slots = c->n_slots;
     P.n_mods_consider = (c->n_mods_consider <= 0 || c->n_mods_consider > M) ? M : c->n_mods_consider;   // qrmsa.pyx:313
     P.row_words = (c->n_slots + 63) / 64;
     P.ext_words = c->n_slots / 64 + 1;
     P.batch = c->batch; P.capacity = c->capacity; P.episode_length = c->episode_length; P.auto_reset = c->auto_reset;
-    P.bit_rate_mode = c->bit_rate_mode; P.n_bit_rates = c->n_bit_rates; P.br_lo = c->bit_rate_lo; P.br_hi = c->bit_rate_hi;
+    P.bit_rate_mode = c->bit_rate_mode; P.br_lo = c->bit_rate_lo; P.br_hi = c->bit_rate_hi;
+    P.n_bit_rates = c->bit_rate_mode == 0 ? c->n_bit_rates : 1;
     P.req_mode = kReqNone;
     P.measure_disruptions = c->measure_disruptions ? 1 : 0;
     P.defragmentation = c->defragmentation ? 1 : 0;
     P.track_ids = (c->defragmentation || c->track_service_ids) ? 1 : 0;
     P.n_defrag_services = c->n_defrag_services;
-    if (c->defragmentation && c->n_defrag_services < 0) return fail_arg(env, "n_defrag_services must be >= 0");
     P.f0 = c->frequency_start; P.slot_bw = c->slot_bandwidth; P.channel_width = c->channel_width;
-    P.nslots_width = c->nslots_channel_width > 0 ? c->nslots_channel_width : c->channel_width;
+    P.nslots_width = T.nslots_width;
     P.mean_holding = c->mean_holding_time;
+    P.mean_holding_f = (float)c->mean_holding_time;
     P.max_bit_rate = c->max_bit_rate;
     if (c->bit_rate_mode == 0) env->cfg_bit_rates.assign(c->bit_rates, c->bit_rates + c->n_bit_rates);
-    P.path_len_norm = nullptr;
-    P.mean_holding_f = (float)c->mean_holding_time;
+    P.uniform_alpha = T.uniform ? 1 : 0;
+    P.rec32 = T.rec32 ? 1 : 0;
+    P.alpha0_cl = T.cl[0];
+    P.ase_shortcut = T.ase_shortcut ? 1 : 0;
+    for (int m = 0; m < M; m++) { P.mod_se[m] = T.mod_se[m]; P.mod_thr[m] = T.mod_thr[m]; P.mod_phi53[m] = T.mod_phi53[m]; }
+    P.tab_nmax = T.tab_nmax; P.tab_stride = T.tab_stride;
+    P.lw_tab_off = T.lw_tab_off; P.lw_tab_bytes = T.lw_tab_bytes;
+    env->path_pair_err = T.path_pair_err;
+    env->admission_pair_err = T.admission_pair_err;
+}
 
-    // derived GN tables in fp64 (core/osnr.pyx:22-24, 52-55, 58-61, 109-125)
-    const double pi = 3.14159265358979323846, beta2 = 21.3e-27, h_planck = 6.626e-34;
-    std::vector<double> w1(E), w2(E), cl(E), selfc(E), ase_link(E);
-    bool uniform = true;
-    for (int e = 0; e < E; e++) {
-        double a = c->link_alpha[e], L = c->link_span_km[e];
-        double l_eff = (1.0 - std::exp(-2.0 * a * L * 1e3)) / (2.0 * a);
-        w1[e] = (double)c->link_nspans[e] * l_eff;
-        w2[e] = (double)c->link_nspans[e] * l_eff * (l_eff / (L * 1e3));
-        cl[e] = pi * pi * beta2 * (1.0 / (2.0 * a));
-        selfc[e] = pi * pi * beta2 / (4.0 * a);
-        ase_link[e] = (double)c->link_nspans[e] * h_planck * (std::exp(2.0 * a * L * 1e3) - 1.0) * c->link_nf[e];
-        if (a != c->link_alpha[0]) uniform = false;
-    }
-    P.uniform_alpha = uniform ? 1 : 0;
-    if (c->measure_disruptions && !uniform) return fail_arg(env, "measure_disruptions needs uniform attenuation", ONGYM_E_LIMIT);
-    if (c->defragmentation && !uniform) return fail_arg(env, "defragmentation needs uniform attenuation", ONGYM_E_LIMIT);
-    if (c->track_service_ids && !uniform) return fail_arg(env, "track_service_ids needs uniform attenuation", ONGYM_E_LIMIT);
-    P.rec32 = (E <= 32 && NP <= 512 && c->n_slots <= 1023) ? 1 : 0;
-    P.alpha0_cl = cl[0];
-    std::vector<uint64_t> mask((size_t)NP * 2, 0);
-    std::vector<double> path_ase(NP, 0.0), path_w1(NP, 0.0);
-    for (int p = 0; p < NP; p++)
-        for (int h = 0; h < c->path_hops[p]; h++) {
-            int l = c->path_links[p * H + h];
-            mask[2 * p + (l >> 6)] |= 1ull << (l & 63);
-            path_ase[p] += ase_link[l];
-            path_w1[p] += w1[l];
-        }
-    std::vector<double> nli_coef((size_t)c->n_slots + 2, 0.0);
-    for (int n = 1; n <= c->n_slots + 1; n++) {
-        const double gamma = 1.3e-3, bwn = c->slot_bandwidth * n;
-        nli_coef[n] = (8.0 / (27.0 * pi * beta2)) * (gamma * gamma) / (bwn * bwn);
-    }
-    std::vector<double> self_asinh((size_t)c->n_slots + 2, 0.0);   // uniform alpha only
-    for (int n = 0; n <= c->n_slots + 1; n++) {
-        double bwn = c->slot_bandwidth * n;
-        self_asinh[n] = std::asinh(selfc[0] * (bwn * bwn));
-    }
-    static const double phi_mod[6] = {1.0, 1.0, 2.0 / 3.0, 17.0 / 25.0, 69.0 / 100.0, 13.0 / 21.0};
-    for (int m = 0; m < M; m++) {
-        P.mod_se[m] = c->mod_se[m];
-        P.mod_thr[m] = c->mod_min_osnr[m];
-        P.mod_phi53[m] = phi_mod[c->mod_se[m] - 1] * (5.0 / 3.0);
-    }
-    // slots needed per (discrete bit rate, modulation): get_number_slots, envs/qrmsa.pyx:1198-1205
-    std::vector<int32_t> nreq_tab((size_t)std::max(c->n_bit_rates, 1) * kMaxMods, 0);
-    if (c->bit_rate_mode == 0)
-        for (int b = 0; b < c->n_bit_rates; b++)
-            for (int m = 0; m < M; m++)
-                nreq_tab[(size_t)b * kMaxMods + m] =
-                    (int32_t)std::ceil((double)(float)c->bit_rates[b] / ((double)c->mod_se[m] * P.nslots_width));
-    // ASE-only rejection is exact iff no interferer term asinh(u)-asinh(v) - Phi*(5/3)*(Bk/|df|)*(l_eff/L) of
-    // core/osnr.pyx:68-93 can be negative: scan the whole discrete domain (slot counts x centre distances in half
-    // slots x modulation formats x distinct link classes) once.
-    {
-        bool all_nonneg = true;
-        std::vector<std::pair<double, double>> classes;   // (cl, l_eff/(L*1e3))
-        for (int e = 0; e < E; e++) {
-            std::pair<double, double> k(cl[e], w2[e] / w1[e]);
-            bool seen = false;
-            for (auto &q : classes) if (q == k) seen = true;
-            if (!seen) classes.push_back(k);
-        }
-        const int S = c->n_slots;
-        for (auto &cls : classes)
-            for (int m = 0; m < M && all_nonneg; m++) {
-                const double K = P.mod_phi53[m] * cls.second;
-                for (int nk = 1; nk <= S && all_nonneg; nk++) {
-                    const double bk = c->slot_bandwidth * nk, ck = cls.first * bk;
-                    for (int dfi = nk + 1; dfi <= 2 * S; dfi++) {
-                        const double adf = 0.5 * c->slot_bandwidth * dfi;
-                        const double t = (std::asinh(ck * (adf + 0.5 * bk)) - std::asinh(ck * (adf - 0.5 * bk))) - K * (bk / adf);
-                        if (!(t > 0.0)) { all_nonneg = false; break; }
-                    }
-                }
-            }
-        P.ase_shortcut = all_nonneg ? 1 : 0;
-    }
+// upload of a whole vector
+template <typename T>
+static int upload(ongym_env *env, const std::vector<T> &v, const T **dst) { return upload(env, v.data(), v.size(), dst); }
+
+// the pair table's two pitched layouts (the first with the link-weight table behind it: freed together), where they exist
+static int upload_pair_layouts(ongym_env *env, const HostTables &T) {
+    if (T.pair_tab2k.empty()) return 0;
+    if (const int rc = upload(env, T.pair_tab2k, &env->P.pair_tab2k)) return rc;
+    return upload(env, T.pair_tabp, &env->P.pair_tabp);
+}
+
+// Every table of the configuration and of HostTables, in the order create has always allocated them.  An optional table that
+// is absent leaves its pointer null and allocates nothing.
+static int upload_tables(ongym_env *env, const ongym_config *c, const HostTables &T) {
+    Params &P = env->P;
+    const size_t N = (size_t)c->n_nodes, NP = (size_t)c->n_paths;
+    const bool discrete = c->bit_rate_mode == 0;
+    const size_t n_rates = discrete ? (size_t)c->n_bit_rates : 1;
+    const double one = 1.0, zero = 0.0;
     int rc;
-    // (asinh difference, Bk/|df|) table of core/osnr.pyx:68-93 for uniform attenuation. Both factors depend only on the
-    // interferer's slot count nk and the centre distance in half slots: precompute them in fp64 with the device's own
-    // expressions. nk range: the largest slot count the configured traffic can produce (anything larger, e.g. from a
-    // replayed trace, is computed on the fly by the kernel).
-    P.pair_tab = nullptr; P.tab_nmax = 0; P.tab_stride = 2 * c->n_slots + 1;
-    P.path_rec = nullptr; P.pair_tab2k = nullptr; P.pair_tabp = nullptr;
-    std::vector<double2> host_tab;
-    if (uniform) {
-        double max_rate = 0.0;
-        if (c->bit_rate_mode == 0) for (int b = 0; b < c->n_bit_rates; b++) max_rate = std::max(max_rate, c->bit_rates[b]);
-        else max_rate = (double)c->bit_rate_hi;
-        int min_se = 6;
-        for (int m = 0; m < M; m++) min_se = std::min(min_se, (int)c->mod_se[m]);
-        int nmax = (int)std::ceil(max_rate / ((double)min_se * P.nslots_width));
-        nmax = std::max(1, std::min(nmax, c->n_slots));
-        size_t entries = (size_t)nmax * P.tab_stride;
-        if (entries * sizeof(double2) <= (size_t)16 << 20) {
-            std::vector<double2> tab(entries);
-            for (int nk = 1; nk <= nmax; nk++) {
-                const double bk = c->slot_bandwidth * nk, ck = cl[0] * bk;
-                for (int d = 0; d < P.tab_stride; d++) {
-                    double2 v; v.x = 0.0; v.y = 0.0;
-                    if (d > nk) {   // allocations never overlap: |df| > Bk/2
-                        const double adf = (0.5 * c->slot_bandwidth) * (double)d;
-                        const double U = ck * (adf + 0.5 * bk), V = ck * (adf - 0.5 * bk);
-                        v.x = std::log((U + std::sqrt(std::fma(U, U, 1.0))) / (V + std::sqrt(std::fma(V, V, 1.0))));
-                        v.y = bk / adf;
-                    }
-                    tab[(size_t)(nk - 1) * P.tab_stride + d] = v;
-                }
-            }
-            if ((rc = upload(env, tab.data(), tab.size(), &P.pair_tab))) return rc;
-            P.tab_nmax = nmax;
-            host_tab.swap(tab);
-        }
-    }
-    if ((rc = upload(env, nreq_tab.data(), nreq_tab.size(), &P.nreq_tab))) return rc;
-    if ((rc = upload(env, c->pair_paths, (size_t)N * N * K, &P.pair_paths))) return rc;
-    {   // route -> node pair for ongym_failure_impact.  Both directions of a pair share their routes in the same order
-        // (topology.pyx:310-355): every pair that lists a route must list the same K routes, or the call refuses
-        std::vector<int32_t> pp((size_t)NP, -1);
-        for (int pr = 0; pr < N * N && env->path_pair_err.empty(); pr++)
-            for (int k = 0; k < K; k++) {
-                const int p = c->pair_paths[(size_t)pr * K + k];
-                if (p < 0) continue;
-                if (pp[p] < 0) pp[p] = pr;
-                else if (pp[p] != pr && !std::equal(c->pair_paths + (size_t)pr * K, c->pair_paths + (size_t)(pr + 1) * K,
-                                                    c->pair_paths + (size_t)pp[p] * K)) {
-                    env->path_pair_err = "route " + std::to_string(p) + " is listed by node pairs " + std::to_string(pp[p]) + " and " +
-                                         std::to_string(pr) + " with different route lists: no node pair for failure impact";
-                    break;
-                }
-            }
-        if ((rc = upload(env, pp.data(), pp.size(), &env->d_path_pair))) return rc;
-    }
-    // ongym_admission_map walks the unordered node pairs: both directions of a pair must list the same routes in the same order
-    for (int s = 0; s < N && env->admission_pair_err.empty(); s++)
-        for (int d = s + 1; d < N; d++)
-            if (!std::equal(c->pair_paths + ((size_t)s * N + d) * K, c->pair_paths + ((size_t)s * N + d + 1) * K,
-                            c->pair_paths + ((size_t)d * N + s) * K)) {
-                env->admission_pair_err = "node pair (" + std::to_string(s) + ", " + std::to_string(d) +
-                                          ") lists different routes in its two directions: no unordered pair for the admission map";
-                break;
-            }
-    if ((rc = upload(env, c->path_hops, (size_t)NP, &P.path_hops))) return rc;
-    if ((rc = upload(env, c->path_links, (size_t)NP * H, &P.path_links))) return rc;
-    if ((rc = upload(env, mask.data(), mask.size(), &P.path_mask))) return rc;
-    if ((rc = upload(env, path_ase.data(), path_ase.size(), &P.path_ase))) return rc;
-    if ((rc = upload(env, path_w1.data(), path_w1.size(), &P.path_w1))) return rc;
-    if ((rc = upload(env, self_asinh.data(), self_asinh.size(), &P.self_asinh))) return rc;
-    if ((rc = upload(env, nli_coef.data(), nli_coef.size(), &P.nli_coef))) return rc;
-    {   // (nli_coef[n], self_asinh[n]) of the slot count of every (discrete bit rate, modulation): lets the request draw
-        // fetch them with the SAME index as nreq_tab instead of a second, dependent round trip through n
-        std::vector<double> rc2(nreq_tab.size() * 2, 0.0);
-        for (size_t i = 0; i < nreq_tab.size(); i++) {
-            const int32_t n = nreq_tab[i];
-            if (n >= 1 && n <= c->n_slots) { rc2[2 * i] = nli_coef[(size_t)n]; rc2[2 * i + 1] = self_asinh[(size_t)n]; }
-        }
-        if ((rc = upload(env, rc2.data(), rc2.size(), &P.req_coef))) return rc;
-    }
-    if ((rc = upload(env, w1.data(), w1.size(), &P.link_w1))) return rc;
-    if ((rc = upload(env, w2.data(), w2.size(), &P.link_w2))) return rc;
-    if ((rc = upload(env, cl.data(), cl.size(), &P.link_cl))) return rc;
-    if ((rc = upload(env, selfc.data(), selfc.size(), &P.link_selfc))) return rc;
-    double one = 1.0, zero = 0.0;
-    if ((rc = upload(env, c->bit_rate_mode == 0 ? c->bit_rates : &zero, c->bit_rate_mode == 0 ? (size_t)c->n_bit_rates : 1, &P.bit_rates))) return rc;
-    if ((rc = upload(env, c->bit_rate_mode == 0 ? c->bit_rate_cum : &one, c->bit_rate_mode == 0 ? (size_t)c->n_bit_rates : 1, &P.bit_rate_cum))) return rc;
-    if (c->bit_rate_mode != 0) P.n_bit_rates = 1;
-    if ((rc = upload(env, c->node_cum, (size_t)N, &P.node_cum))) return rc;
-    if (c->path_len_norm && (rc = upload(env, c->path_len_norm, (size_t)NP, &P.path_len_norm))) return rc;
-    {   // link_shannon_entropy_ (utils.pyx:61-79): p = block / total_slots; p * math.log(p) — CPython's math.log is this log()
-        std::vector<double> plogp((size_t)c->n_slots + 1, 0.0);
-        for (int n = 1; n <= c->n_slots; n++) { const double pr = (double)n / (double)c->n_slots; plogp[n] = pr * std::log(pr); }
-        if ((rc = upload(env, plogp.data(), plogp.size(), &P.plogp))) return rc;
-    }
+    if (!T.pair_tab.empty() &&
+        (rc = upload(env, reinterpret_cast<const double2 *>(T.pair_tab.data()), T.pair_tab.size() / 2, &P.pair_tab))) return rc;
+    if ((rc = upload(env, T.nreq_tab, &P.nreq_tab))) return rc;
+    if ((rc = upload(env, c->pair_paths, N * N * c->k_paths, &P.pair_paths))) return rc;
+    if ((rc = upload(env, T.path_pair, &env->d_path_pair))) return rc;
+    if ((rc = upload(env, c->path_hops, NP, &P.path_hops))) return rc;
+    if ((rc = upload(env, c->path_links, NP * c->max_hops, &P.path_links))) return rc;
+    if ((rc = upload(env, T.path_mask, &P.path_mask))) return rc;
+    if ((rc = upload(env, T.path_ase, &P.path_ase))) return rc;
+    if ((rc = upload(env, T.path_w1, &P.path_w1))) return rc;
+    if ((rc = upload(env, T.self_asinh, &P.self_asinh))) return rc;
+    if ((rc = upload(env, T.nli_coef, &P.nli_coef))) return rc;
+    if ((rc = upload(env, T.req_coef, &P.req_coef))) return rc;
+    if ((rc = upload(env, T.w1, &P.link_w1))) return rc;
+    if ((rc = upload(env, T.w2, &P.link_w2))) return rc;
+    if ((rc = upload(env, T.cl, &P.link_cl))) return rc;
+    if ((rc = upload(env, T.selfc, &P.link_selfc))) return rc;
+    if ((rc = upload(env, discrete ? c->bit_rates : &zero, n_rates, &P.bit_rates))) return rc;
+    if ((rc = upload(env, discrete ? c->bit_rate_cum : &one, n_rates, &P.bit_rate_cum))) return rc;
+    if ((rc = upload(env, c->node_cum, N, &P.node_cum))) return rc;
+    if (c->path_len_norm && (rc = upload(env, c->path_len_norm, NP, &P.path_len_norm))) return rc;
+    if ((rc = upload(env, T.plogp, &P.plogp))) return rc;
+    return upload_pair_layouts(env, T);
+}
 
-    // the pair table once more with a row pitch of 2048 entries (index = row << 11 | distance: one address instruction);
-    // used by the lean first-fit kernel and by the observation field builder
-    LwTable lwt;
-    P.lw_tab_off = 0; P.lw_tab_bytes = 0;
-    if (!host_tab.empty() && P.tab_stride < kTabPitch && (size_t)P.tab_nmax * kTabPitch * 16 <= ((size_t)64 << 20)) {
-        std::vector<double> t2((size_t)P.tab_nmax * kTabPitch * 2, 0.0);
-        for (int nk = 0; nk < P.tab_nmax; nk++)
-            for (int d = 0; d < P.tab_stride; d++) {
-                t2[((size_t)nk * kTabPitch + d) * 2] = host_tab[(size_t)nk * P.tab_stride + d].x;
-                t2[((size_t)nk * kTabPitch + d) * 2 + 1] = host_tab[(size_t)nk * P.tab_stride + d].y;
-            }
-        // ... and behind it the shared-link weight table of the lean kernels (ongym_lwtab.hpp), when the links fit one mask word.
-        // One allocation: the kernels gather from both tables through the same base register.  It is freed with the pair table.
-        const char *no_lw = std::getenv("ONGYM_FAST_NO_LWTAB");
-        if (P.rec32 && E <= 32 && !(no_lw && no_lw[0] == '1')) {
-            std::vector<uint32_t> m32((size_t)NP);
-            for (int p = 0; p < NP; p++) m32[(size_t)p] = (uint32_t)mask[2 * p];
-            lwt = lw_build(m32, w1.data(), w2.data(), t2.size() * 8);
-            if (lwt.ok) {
-                P.lw_tab_off = (uint32_t)(t2.size() * 8); P.lw_tab_bytes = (uint32_t)(lwt.entries.size() * 8);
-                t2.insert(t2.end(), lwt.entries.begin(), lwt.entries.end());
-            }
+// Lean kernels (ongym_fast.hpp): whether the configuration is eligible, as far as that needs no table on the device
+static bool lean_eligible(const Params &P, const ongym_config *c, const CreateKnobs &knobs, const HostTables &T, size_t flds) {
+    bool ok = T.uniform && P.ase_shortcut && !P.track_ids && !P.measure_disruptions && c->bit_rate_mode == 0 &&
+              P.n_mods_consider == c->n_mods &&
+              c->n_bit_rates <= 8 && c->n_links <= 32 + (int)kM64HiBits && c->n_nodes <= 64 && P.pair_tab2k != nullptr;
+    if (knobs.force_generic) ok = false;
+    if (ok) {
+        for (int b = 0; b < c->n_bit_rates; b++) {
+            const double r = c->bit_rates[b];
+            if (!(r > 0) || r != std::floor(r) || r > 16777216.0) ok = false;   // integer-valued, exact as float32
         }
-        if ((rc = upload(env, t2.data(), t2.size(), &P.pair_tab2k))) return rc;
-        std::vector<double> t3((size_t)P.tab_nmax * kTabPitch * 2, 0.0);
-        for (int nk = 0; nk < P.tab_nmax; nk++)
-            for (int d = 0; d < P.tab_stride; d++) {
-                const size_t e = (size_t)nk * kTabPitch + (size_t)(d & 1) * (kTabPitch / 2) + (size_t)(d >> 1);
-                t3[e * 2] = host_tab[(size_t)nk * P.tab_stride + d].x;
-                t3[e * 2 + 1] = host_tab[(size_t)nk * P.tab_stride + d].y;
-            }
-        if ((rc = upload(env, t3.data(), t3.size(), &P.pair_tabp))) return rc;
+        if (T.max_n < 1 || T.max_n > 512 || T.max_n > P.tab_nmax) ok = false;
     }
-    // ---- lean first-fit kernel (ongym_fast.hpp): eligibility and its path table ----
-    {
-        bool ok = uniform && P.ase_shortcut && !P.track_ids && !P.measure_disruptions && c->bit_rate_mode == 0 &&
-                  P.n_mods_consider == M &&
-                  c->n_bit_rates <= 8 && E <= 32 + (int)kM64HiBits && N <= 64 && P.pair_tab2k != nullptr;
-        const char *force = std::getenv("ONGYM_FORCE_GENERIC");
-        if (force && force[0] == '1') ok = false;
-        int max_n = 0;
-        if (ok) {
-            for (int b = 0; b < c->n_bit_rates; b++) {
-                const double r = c->bit_rates[b];
-                if (!(r > 0) || r != std::floor(r) || r > 16777216.0) ok = false;   // integer-valued, exact as float32
-                for (int m = 0; m < M; m++) max_n = std::max(max_n, std::min((int)nreq_tab[(size_t)b * kMaxMods + m], (int)c->n_slots));
-            }
-            if (max_n < 1 || max_n > 512 || max_n > P.tab_nmax) ok = false;
-        }
-        const bool m64 = !P.rec32;
-        const size_t flds = fast_lds_bytes(E, P.row_words, c->capacity, m64);
-        if (flds > 160 * 1024) ok = false;
-        P.path_hash_keys = nullptr; P.path_hash_vals = nullptr; P.path_hash_bits = 0; P.pad_hash = 0;
-        if (ok && m64) {
-            // the M64 record keeps the link set (<= 32 + kM64HiBits bits) instead of the path id: it must identify the route
-            int bits = 4;
-            while ((1 << bits) < 4 * NP) bits++;
-            std::vector<uint64_t> keys((size_t)1 << bits, ~0ull);
-            std::vector<int32_t> vals((size_t)1 << bits, -1);
-            for (int p = 0; p < NP && ok; p++) {
-                const uint64_t key = mask[2 * p];
-                uint32_t h = path_hash_slot(key, bits);
-                while (keys[h] != ~0ull && keys[h] != key) h = (h + 1u) & ((1u << bits) - 1u);
-                if (keys[h] == key) ok = false;          // two path ids with the same link set: keep the generic kernel
-                keys[h] = key; vals[h] = p;
-            }
-            if (ok) {
-                if ((rc = upload(env, keys.data(), keys.size(), &P.path_hash_keys))) return rc;
-                if ((rc = upload(env, vals.data(), vals.size(), &P.path_hash_vals))) return rc;
-                P.path_hash_bits = bits;
-            }
-        }
-        if (ok) {
-            std::vector<PathRec> recs((size_t)NP);
-            for (int p = 0; p < NP; p++) {
-                PathRec &r = recs[(size_t)p];
-                r.hops = (uint32_t)c->path_hops[p]; r.mask_lo = (uint32_t)mask[2 * p];
-                r.mask_hi = (uint32_t)(mask[2 * p] >> 32);
-                r.id = (uint32_t)p; r.ase = path_ase[(size_t)p]; r.w1 = path_w1[(size_t)p];
-                // one mask word: mask_hi is 0 and no lean kernel reads `id` from the record (first fit knows the route it fetched,
-                // the other policies take it from pair_paths), so the two dwords carry the route's weight-table multiplier and
-                // block (see PathRec) and arrive with the same scalar load.  Kernels that sum over the links ignore both.
-                if (!m64 && P.lw_tab_bytes) { r.mask_hi = lwt.mult[(size_t)p]; r.id = lwt.loc[(size_t)p]; }
-            }
-            const PathRec *d_recs = nullptr;
-            if ((rc = upload(env, recs.data(), recs.size(), &d_recs))) return rc;
-            P.path_rec = d_recs;
-            env->fast_ok = true; env->fast_m64 = m64; env->fast_lds = flds;
-            // every record the lean kernels ever see carries a slot count of the traffic table (records written by the other
-            // entry points included: eligibility demands discrete bit rates): none above 32 -> the narrow build
-            const char *fw = std::getenv("ONGYM_FORCE_WIDE");
-            env->fast_wide = max_n > 32 || (fw && fw[0] == '1');
-        }
-    }
+    return ok && flds <= 160 * 1024;
+}
 
-    // mutable state
+// The M64 record keeps the link set (<= 32 + kM64HiBits bits) instead of the path id: it must identify the route.
+// *ok = false, and nothing uploaded: two path ids with the same link set, the generic kernel stays.
+static int upload_path_hash(ongym_env *env, const HostTables &T, bool *ok) {
+    Params &P = env->P;
+    const int NP = P.n_paths;
+    int bits = 4, rc;
+    while ((1 << bits) < 4 * NP) bits++;
+    std::vector<uint64_t> keys((size_t)1 << bits, ~0ull);
+    std::vector<int32_t> vals((size_t)1 << bits, -1);
+    for (int p = 0; p < NP && *ok; p++) {
+        const uint64_t key = T.path_mask[2 * p];
+        uint32_t h = path_hash_slot(key, bits);
+        while (keys[h] != ~0ull && keys[h] != key) h = (h + 1u) & ((1u << bits) - 1u);
+        if (keys[h] == key) *ok = false;
+        keys[h] = key; vals[h] = p;
+    }
+    if (!*ok) return 0;
+    if ((rc = upload(env, keys, &P.path_hash_keys))) return rc;
+    if ((rc = upload(env, vals, &P.path_hash_vals))) return rc;
+    P.path_hash_bits = bits;
+    return 0;
+}
+
+// Lean kernels: eligibility (env->fast_ok), the M64 path hash and the PathRec table
+static int build_lean(ongym_env *env, const ongym_config *c, const CreateKnobs &knobs, const HostTables &T) {
+    Params &P = env->P;
+    const int NP = c->n_paths;
+    const bool m64 = !P.rec32;
+    const size_t flds = fast_lds_bytes(c->n_links, P.row_words, c->capacity, m64);
+    bool ok = lean_eligible(P, c, knobs, T, flds);
+    int rc;
+    if (ok && m64 && (rc = upload_path_hash(env, T, &ok))) return rc;
+    if (!ok) return 0;
+    std::vector<PathRec> recs((size_t)NP);
+    for (int p = 0; p < NP; p++) {
+        PathRec &r = recs[(size_t)p];
+        r.hops = (uint32_t)c->path_hops[p]; r.mask_lo = (uint32_t)T.path_mask[2 * p];
+        r.mask_hi = (uint32_t)(T.path_mask[2 * p] >> 32);
+        r.id = (uint32_t)p; r.ase = T.path_ase[(size_t)p]; r.w1 = T.path_w1[(size_t)p];
+        // one mask word: mask_hi is 0 and no lean kernel reads `id` from the record (first fit knows the route it fetched,
+        // the other policies take it from pair_paths), so the two dwords carry the route's weight-table multiplier and
+        // block (see PathRec) and arrive with the same scalar load.  Kernels that sum over the links ignore both.
+        if (!m64 && P.lw_tab_bytes) { r.mask_hi = T.lw_mult[(size_t)p]; r.id = T.lw_loc[(size_t)p]; }
+    }
+    const PathRec *d_recs = nullptr;
+    if ((rc = upload(env, recs, &d_recs))) return rc;
+    P.path_rec = d_recs;
+    env->fast_ok = true; env->fast_m64 = m64; env->fast_lds = flds;
+    // every record the lean kernels ever see carries a slot count of the traffic table (records written by the other
+    // entry points included: eligibility demands discrete bit rates): none above 32 -> the narrow build
+    env->fast_wide = T.max_n > 32 || knobs.force_wide;
+    return 0;
+}
+
+// every replica's DevEnv, and bitmaps that start "all free" so that queries before the first reset see an empty network
+static int init_state(ongym_env *env, const ongym_config *c) {
+    Params &P = env->P;
     const size_t B = (size_t)c->batch;
-    if ((rc = dev_alloc(env, B * E * P.row_words, &P.occ, true))) return rc;
-    if ((rc = dev_alloc(env, B * c->capacity, &P.svc_a, true))) return rc;
-    if ((rc = dev_alloc(env, B * c->capacity, &P.svc_b, true))) return rc;
-    if ((rc = dev_alloc(env, B * c->capacity, &P.svc_r, true))) return rc;
-    P.svc_q = nullptr; P.svc_o = nullptr; P.move_log = nullptr; P.move_n = nullptr;
-    if (P.track_ids) {
-        if ((rc = dev_alloc(env, B * c->capacity, &P.svc_q, true))) return rc;
-        if ((rc = dev_alloc(env, B * c->capacity, &P.svc_o, true))) return rc;
-        if ((rc = dev_alloc(env, B * ONGYM_MOVE_LOG, &P.move_log, true))) return rc;
-        if ((rc = dev_alloc(env, B, &P.move_n, true))) return rc;
-    }
-    if ((rc = dev_alloc(env, B, &P.env, false))) return rc;
     std::vector<DevEnv> host(B);
     memset(host.data(), 0, B * sizeof(DevEnv));
     for (size_t r = 0; r < B; r++) {
@@ -908,34 +736,66 @@ static int build(ongym_env *env, const ongym_config *c) {
         d.launch_power = c->replica_launch_power_w ? c->replica_launch_power_w[r] : c->launch_power_w;
         d.margin = c->replica_margin ? c->replica_margin[r] : c->margin;
         double load = c->replica_load ? c->replica_load[r] : c->load;
-        if (!(load > 0) || !(d.launch_power > 0)) return fail_arg(env, "per-replica load / launch power must be positive");
         d.mean_iat = 1 / (load / c->mean_holding_time);   // set_load, envs/qrmsa.pyx:1124-1132
         d.mean_iat_f = (float)d.mean_iat;
     }
     HIP_TRY(env, hipMemcpy(P.env, host.data(), B * sizeof(DevEnv), hipMemcpyHostToDevice));
-    // the bitmaps start "all free" so that queries before the first reset see an empty network
-    {
-        std::vector<uint64_t> row(P.row_words);
-        for (int w = 0; w < P.row_words; w++) {
-            int a = 0, b = std::min(c->n_slots - 64 * w, 64);
-            row[w] = b >= 64 ? ~0ull : ((1ull << b) - 1ull);
-            (void)a;
-        }
-        std::vector<uint64_t> all(B * E * P.row_words);
-        for (size_t i = 0; i < all.size(); i++) all[i] = row[i % P.row_words];
-        HIP_TRY(env, hipMemcpy(P.occ, all.data(), all.size() * 8, hipMemcpyHostToDevice));
+    std::vector<uint64_t> row(P.row_words);
+    for (int w = 0; w < P.row_words; w++) {
+        const int b = std::min(c->n_slots - 64 * w, 64);
+        row[w] = b >= 64 ? ~0ull : ((1ull << b) - 1ull);
     }
+    std::vector<uint64_t> all(B * c->n_links * P.row_words);
+    for (size_t i = 0; i < all.size(); i++) all[i] = row[i % P.row_words];
+    HIP_TRY(env, hipMemcpy(P.occ, all.data(), all.size() * 8, hipMemcpyHostToDevice));
+    return 0;
+}
+
+// The mutable state: the arrays and their initial contents
+static int alloc_state(ongym_env *env, const ongym_config *c) {
+    Params &P = env->P;
+    const size_t B = (size_t)c->batch, E = (size_t)c->n_links;
+    int rc;
+    if ((rc = dev_alloc(env, B * E * P.row_words, &P.occ, true))) return rc;
+    if ((rc = dev_alloc(env, B * c->capacity, &P.svc_a, true))) return rc;
+    if ((rc = dev_alloc(env, B * c->capacity, &P.svc_b, true))) return rc;
+    if ((rc = dev_alloc(env, B * c->capacity, &P.svc_r, true))) return rc;
+    if (P.track_ids) {
+        if ((rc = dev_alloc(env, B * c->capacity, &P.svc_q, true))) return rc;
+        if ((rc = dev_alloc(env, B * c->capacity, &P.svc_o, true))) return rc;
+        if ((rc = dev_alloc(env, B * ONGYM_MOVE_LOG, &P.move_log, true))) return rc;
+        if ((rc = dev_alloc(env, B, &P.move_n, true))) return rc;
+    }
+    if ((rc = dev_alloc(env, B, &P.env, false))) return rc;
+    if ((rc = init_state(env, c))) return rc;
     env->lds = lds_bytes(P);   // the launches raise their kernel's LDS limit above 64 KiB (launch_lds)
     if (env->lds > 160 * 1024) return fail_arg(env, "state does not fit the 160 KiB LDS: lower capacity", ONGYM_E_LIMIT);
-    if (env->fast_ok) {   // the lean units: LDS limits; a policy whose block does not fit the CU keeps the generic kernel
-        for (const auto &u : kLeanUnits) {
-            if (env->fast_ok && (env->fast_wide ? u.wide : u.narrow).prepare(env) == 0) env->lean_policies |= 1u << u.policy;
-            else if (u.policy == ONGYM_POLICY_FIRST_FIT) env->fast_ok = false;
-        }
-        env->err.clear();
+    return 0;
+}
+
+// the lean units: LDS limits; a policy whose block does not fit the CU keeps the generic kernel
+static void prepare_lean(ongym_env *env) {
+    if (!env->fast_ok) return;
+    for (const auto &u : kLeanUnits) {
+        if (env->fast_ok && (env->fast_wide ? u.wide : u.narrow).prepare(env) == 0) env->lean_policies |= 1u << u.policy;
+        else if (u.policy == ONGYM_POLICY_FIRST_FIT) env->fast_ok = false;
     }
+    env->err.clear();
+}
+
+static int build(ongym_env *env, const ongym_config *c) {
+    int rc;
+    if ((rc = config_check(*c, env->err))) return rc;
+    const CreateKnobs knobs = read_knobs(env);
+    HostTables T;
+    derive_tables(*c, knobs, kTabPitch, T);
+    set_params(env, c, T);
+    if ((rc = upload_tables(env, c, T))) return rc;
+    if ((rc = build_lean(env, c, knobs, T))) return rc;
+    if ((rc = alloc_state(env, c))) return rc;
+    prepare_lean(env);
 #ifdef ONGYM_STAMPS
-    if ((rc = dev_alloc(env, 16, &P.dbg, true))) return rc;
+    if ((rc = dev_alloc(env, 16, &env->P.dbg, true))) return rc;
 #endif
     if ((rc = dev_alloc(env, 1, &env->d_P, false))) return rc;
     return push_params(env);

@@ -45,10 +45,10 @@ struct ongym_env {
     bool has_source = false;
     uint64_t replica_base = 0;      // global index of this environment's first replica (ongym_seed_base)
     std::vector<double> cfg_bit_rates;     // host copy of the discrete bit rates
-    bool fast_ok = false;           // the configuration is eligible for k_fast (decided in build(), ongym_hip.hip)
+    bool fast_ok = false;           // the configuration is eligible for k_fast (decided in build_lean(), ongym_hip.hip)
     bool fast_m64 = false;
     bool fast_wide = true;          // some slot count of the traffic table exceeds 32: the general (`w`) lean kernels run
-    uint32_t lean_policies = 0;     // bit p: policy p's lean unit prepared in build() (its LDS block fits the CU)
+    uint32_t lean_policies = 0;     // bit p: policy p's lean unit prepared at create (its LDS block fits the CU)
     bool trace_used = false;        // a trace the lean kernel cannot replay was installed: its records may not fit the lean codec
     bool trace_fast_ok = false;     // the installed (host) trace only carries bit rates of the configured table
     size_t fast_lds = 0;
