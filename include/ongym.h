@@ -768,6 +768,13 @@ int ongym_query_occupancy_policy(ongym_env *env, int32_t policy, int32_t *blocks
  * computes, out[3] = the number of index bits W; entry[0..1] = (sum w1, sum w2) as read back from device memory at the address
  * the kernel would use.  ONGYM_E_ARG: path outside 0..n_paths-1 or a NULL pointer. */
 int ongym_query_link_weight_entry(ongym_env *env, int32_t path, uint32_t links, uint32_t out[4], double entry[2]);
+/* Diagnostic, read-only: dword 0 of route `path` in first fit's copy of the route records, as read back from device memory
+ * (csrc/ongym_tables.hpp, path_rows_word).  Bits 0..7 = the hop count; four fields 6 bits apart from bit 8 (link ids < 32: five bits each
+ * count) = the route's links in path_links order, the first link repeated behind the last hop; bit 31 (the spare bit of the
+ * last field) = the route takes the link loop (more than four
+ * hops, n_slots >= 512 or n_links > 32), its fields are then 0.  ONGYM_E_ARG: path outside 0..n_paths-1, a NULL pointer or an
+ * environment without lean kernels. */
+int ongym_query_path_rows(ongym_env *env, int32_t path, uint32_t *out);
 int ongym_sync(ongym_env *env);
 /* Run every later call of this environment on the CALLER's HIP stream (a hipStream_t passed as void *, e.g. PyTorch-ROCm's
  * torch.cuda.current_stream().cuda_stream) instead of the environment's own: the environment's launches are then ordered with

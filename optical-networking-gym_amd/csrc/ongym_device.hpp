@@ -126,6 +126,9 @@ struct Params {
     const ongym_request *trace;
     long long trace_n;
     unsigned long long *dbg;   // diagnostic build only (-DONGYM_STAMPS): per-phase cycle sums
+    // (last, so that no other field moves) first fit's copy of path_rec, dword 0 = path_rows_word (ongym_tables.hpp): read only by
+    // the lean first-fit kernels without records and with one mask word
+    const void *path_rec_ff;        // PathRec [P]
 };
 
 // ---------------------------------------------------------------------------------------------------------------

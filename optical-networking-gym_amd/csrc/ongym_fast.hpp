@@ -51,6 +51,9 @@ namespace ongym {
 
 constexpr int kTabPitch = 2048;      // pair-table row pitch (2S+1 <= 2047)
 constexpr int kNearHalfSlots = 32;   // candidate-lane evaluation: interferers this close to the pass's candidates are staged first
+// dword 0 of a record of Params::path_rec_ff (ongym_tables.hpp holds the same values as kCfgPathRows*; ongym_hip.hip asserts it)
+constexpr uint32_t kPathRowsLong = 1u << 31;
+constexpr int kPathRowsShift = 8, kPathRowsBits = 6, kPathRowsLanes = 16;
 
 // ---- path record (8 dwords, 32-byte aligned: one s_load_dwordx8) -------------------------------------------------------
 struct PathRec {
@@ -510,7 +513,10 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
         cur_bi = hit ? __builtin_ctzll(hit) : 0;
     }
     int cur_p0 = uniform_i32(KC(P.pair_paths)[pair_base()]);
-    const __attribute__((address_space(4))) PathRec *const path_recs = KC(reinterpret_cast<const PathRec *>(P.path_rec));
+    // (first fit without records, one mask word - kFrRows below - reads its copy of the records, whose dword 0 spells out the links)
+    constexpr bool kFrRows = POL == ONGYM_POLICY_FIRST_FIT && !REC && !M64;
+    const __attribute__((address_space(4))) PathRec *const path_recs =
+        KC(reinterpret_cast<const PathRec *>(kFrRows ? P.path_rec_ff : P.path_rec));
     // launch deltas
     // (not counted per step: requests popped = the advance of the request index; steps = the advance of the step loop, except for a
     //  replayed trace, whose exhausted steps do not count; modulations settled by the bound = M x routes examined - d_feas with first fit)
@@ -602,9 +608,26 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
 
     // AND of the free bitmaps of a path's links, extended by the virtual free slot S (see path_free_ext); the links come
     // from the path's mask (their order does not matter)
-    auto path_and = [&](uint64_t links64) -> uint32_t {
-        const int wl = min(lane, RW - 1);
+    //
+    // kFrRows (first fit without records, one mask word; DESIGN.md section 5, "Route rows in one trip"): the kernel's records come
+    // from Params::path_rec_ff, whose dword 0 (`rows`; path_rows_word, ongym_tables.hpp) spells out the links of a route of up to
+    // four hops.  Lane 16 r + w then reads word w of the row of field r: one ds_read_b32 for all hops, and two lane swaps with an
+    // AND each leave the AND of the four rows in every row of 16 lanes; no scalar loop.  Fields behind the last hop repeat the
+    // first link.  A route marked long (sign bit) takes the link loop, where lanes 16 and up read copies that stay 0.
+    auto path_and = [&](uint64_t links64, uint32_t rows = kPathRowsLong) -> uint32_t {
+        const int wl = kFrRows && RW <= kPathRowsLanes ? min(lane & (kPathRowsLanes - 1), RW - 1) : min(lane, RW - 1);
         uint32_t x = lane < RW ? ~0u : 0u;
+        if (kFrRows && (int32_t)rows >= 0) {
+            const uint32_t l = __builtin_amdgcn_ubfe(rows, (uint32_t)(lane >> 4) * kPathRowsBits + kPathRowsShift, 5u);
+            uint32_t y = *(const __attribute__((address_space(3))) uint32_t *)(uintptr_t)
+                             (__umul24(l, vz + (uint32_t)RW * 4u) + occ_base + (uint32_t)wl * 4u);
+            const auto h = __builtin_amdgcn_permlane16_swap(y, y, false, false);    // rows 0 1 2 3 -> 0 0 2 2 | 1 1 3 3
+            y = h[0] & h[1];
+            const auto f = __builtin_amdgcn_permlane32_swap(y, y, false, false);    // halves lo hi -> lo lo | hi hi
+            x &= f[0] & f[1];
+            if (lane == (S >> 5)) x |= 1u << (S & 31);
+            return x;
+        }
         // Two links per trip while two remain: both rows are read before either is used, so a pair costs one LDS round trip
         // (the same instructions per link; no neutral read pads an odd count).  kFrPathAnd: every caller passes the mask of a real
         // route (hops >= 1), so the loop is entered without testing `links` first.
@@ -918,7 +941,7 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
             if (kFrRoute0) {
                 path = fr_path;
                 pr = load_path_rec(path_recs, path);
-                d_paths++; d_hops += pr.hops;
+                d_paths++; d_hops += kFrRows ? pr.hops & 0xFFu : pr.hops;
             } else if (POL == ONGYM_POLICY_FIRST_FIT) {
                 path = k == 0 ? cur_p0 : uniform_i32(KC(P.pair_paths)[pair_base() + k]);
                 if (path < 0) break;
@@ -947,7 +970,7 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
             FSTAMP(0);
             if (!feas) continue;
             const uint64_t pmask = mask_of(pr);
-            uint32_t runs = path_and(pmask);
+            uint32_t runs = path_and(pmask, pr.hops);
             FSTAMP(1);
             // the route's block of the shared-link weight table (PathRec)
             uint32_t lw_mult = 0, lw_loc = 0;
@@ -1446,7 +1469,7 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                     const int path = uniform_i32(KC(P.pair_paths)[pair_base() + k]);
                     if (path < 0) break;
                     const PathRec pr = load_path_rec(path_recs, path);
-                    const uint32_t x = path_and(M64 ? ((uint64_t)pr.mask_lo | ((uint64_t)(pr.mask_hi & 0x1FFu) << 32)) : (uint64_t)pr.mask_lo);
+                    const uint32_t x = path_and(M64 ? ((uint64_t)pr.mask_lo | ((uint64_t)(pr.mask_hi & 0x1FFu) << 32)) : (uint64_t)pr.mask_lo, pr.hops);
                     int r1 = 1;
                     if (first_set32(run_and32<WIDE>(x, r1, n_small + 1)) >= 0) bosnr = 1;
                 }
@@ -1467,7 +1490,7 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                     const int path = uniform_i32(KC(P.pair_paths)[pair_base() + k]);
                     if (path < 0) break;
                     const PathRec pr = load_path_rec(path_recs, path);
-                    const uint32_t x = path_and(M64 ? ((uint64_t)pr.mask_lo | ((uint64_t)(pr.mask_hi & 0x1FFu) << 32)) : (uint64_t)pr.mask_lo);
+                    const uint32_t x = path_and(M64 ? ((uint64_t)pr.mask_lo | ((uint64_t)(pr.mask_hi & 0x1FFu) << 32)) : (uint64_t)pr.mask_lo, pr.hops);
                     int r1 = 1;
                     const bool any = first_set32(run_and32<WIDE>(x, r1, n_small + 1)) >= 0;
                     if (any) { bosnr = 1; bres = 0; }

@@ -575,6 +575,9 @@ static CreateKnobs read_knobs(ongym_env *env) {
 // ---- create: config_check and derive_tables (ongym_tables.hpp, no device needed), then the steps below in build()'s order.
 // The device allocations and copies keep one fixed sequence: where the state arrays lie is part of what gets timed. ----
 static_assert(kCfgMaxMods == kMaxMods && kCfgMaxLinks == kMaxLinks && kCfgMaxHops == kMaxHops, "ongym_tables.hpp checks other limits");
+static_assert(kCfgPathRowsLong == kPathRowsLong && kCfgPathRowsShift == kPathRowsShift && kCfgPathRowsBits == kPathRowsBits &&
+              kCfgPathRowsLanes == kPathRowsLanes && kCfgPathRowsFields * kPathRowsLanes == kWave,
+              "ongym_tables.hpp packs the route rows otherwise than path_and unpacks them");
 
 // the scalar fields of Params and the per-format tables
 static void set_params(ongym_env *env, const ongym_config *c, const HostTables &T) {
@@ -718,6 +721,10 @@ static int build_lean(ongym_env *env, const ongym_config *c, const CreateKnobs &
     const PathRec *d_recs = nullptr;
     if ((rc = upload(env, recs, &d_recs))) return rc;
     P.path_rec = d_recs;
+    // first fit's copy: the same records with the route's links spelled out in dword 0 (path_rows_word, ongym_tables.hpp)
+    for (int p = 0; p < NP; p++) recs[(size_t)p].hops = path_rows_word(c, p);
+    if ((rc = upload(env, recs, &d_recs))) return rc;
+    P.path_rec_ff = d_recs;
     env->fast_ok = true; env->fast_m64 = m64; env->fast_lds = flds;
     // every record the lean kernels ever see carries a slot count of the traffic table (records written by the other
     // entry points included: eligibility demands discrete bit rates): none above 32 -> the narrow build
@@ -1076,6 +1083,15 @@ int ongym_query_link_weight_entry(ongym_env *env, int32_t path, uint32_t links, 
         return fail_arg(env, "weight-table entry outside the table");
     HIP_TRY(env, hipMemcpy(entry, reinterpret_cast<const char *>(env->P.pair_tab2k) + off, 16, hipMemcpyDeviceToHost));
     out[0] = 1; out[1] = mult; out[2] = idx; out[3] = 32u - (loc & 31u);
+    return ONGYM_OK;
+}
+
+int ongym_query_path_rows(ongym_env *env, int32_t path, uint32_t *out) {
+    if (!env || !out) return ONGYM_E_ARG;
+    if (path < 0 || path >= env->P.n_paths) return fail_arg(env, "path out of range");
+    if (!env->fast_ok) return fail_arg(env, "no lean kernel, no route-row table");
+    HIP_TRY(env, hipSetDevice(env->cfg.device));
+    HIP_TRY(env, hipMemcpy(out, static_cast<const PathRec *>(env->P.path_rec_ff) + path, sizeof(*out), hipMemcpyDeviceToHost));
     return ONGYM_OK;
 }
 

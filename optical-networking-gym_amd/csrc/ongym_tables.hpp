@@ -323,6 +323,23 @@ inline void derive_admission_pairs(const ongym_config *c, HostTables &T) {
             }
 }
 
+// Dword 0 of a route's record in first fit's copy of the record table (Params::path_rec_ff; ongym_fast.hpp, path_and): the hop
+// count in the low byte and above it four 6-bit fields with the route's links in path_links order, so that the kernel reads the
+// rows of all hops in one LDS trip (lane 16 r + w = word w of the row of field r).  Fields past the last hop repeat the first
+// link: the AND of the rows is idempotent.  kCfgPathRowsLong marks a route for the link loop, its fields are 0: more than four
+// hops, a row that with the virtual slot S does not fit 16 lanes (S >= 512), or link ids beyond one mask word.
+constexpr uint32_t kCfgPathRowsLong = 1u << 31;
+constexpr int kCfgPathRowsFields = 4, kCfgPathRowsShift = 8, kCfgPathRowsBits = 6, kCfgPathRowsLanes = 16;
+inline uint32_t path_rows_word(const ongym_config *c, int p) {
+    const int hops = c->path_hops[p];
+    const uint32_t w = (uint32_t)hops & 0xFFu;
+    if (hops > kCfgPathRowsFields || c->n_slots / 32 + 1 > kCfgPathRowsLanes || c->n_links > 32) return w | kCfgPathRowsLong;
+    uint32_t f = 0;
+    for (int r = 0; r < kCfgPathRowsFields; r++)
+        f |= (uint32_t)c->path_links[(size_t)p * c->max_hops + (r < hops ? r : 0)] << (kCfgPathRowsShift + kCfgPathRowsBits * r);
+    return w | f;
+}
+
 // `c` has passed config_check.  tab_pitch: kTabPitch of ongym_fast.hpp.
 inline void derive_tables(const ongym_config &c, const CreateKnobs &knobs, int tab_pitch, HostTables &T) {
     derive_links(&c, T);

@@ -297,6 +297,9 @@ def _declare(lib):
     if hasattr(lib, "ongym_query_link_weight_entry"):       # (absent from an older build named by ONGYM_HIP_LIB)
         lib.ongym_query_link_weight_entry.argtypes = [vp, C.c_int32, C.c_uint32, vp, vp]
         lib.ongym_query_link_weight_entry.restype = C.c_int32
+    if hasattr(lib, "ongym_query_path_rows"):
+        lib.ongym_query_path_rows.argtypes = [vp, C.c_int32, vp]
+        lib.ongym_query_path_rows.restype = C.c_int32
     if os.environ.get("ONGYM_HIP_LIB") and not hasattr(lib, "ongym_query_occupancy_policy"):
         # an older experiment build named by ONGYM_HIP_LIB (tools/ab_bench.py): first fit only
         lib.ongym_query_occupancy_policy = lambda h, policy, nb, lds, lean: lib.ongym_query_occupancy(h, nb, lds, lean)
@@ -330,7 +333,7 @@ EXPORTED_SYMBOLS = (
     "ongym_masked_categorical_rows", "ongym_masked_categorical_backward_rows", "ongym_gae", "ongym_state_size", "ongym_state_save", "ongym_state_load", "ongym_fork", "ongym_query_available", "ongym_query_gsnr", "ongym_query_gsnr_many", "ongym_query_moves", "ongym_query_grid",
     "ongym_query_services", "ongym_query_request", "ongym_query_candidates", "ongym_query_path_free",
     "ongym_stats_get", "ongym_sync", "ongym_set_stream", "ongym_last_kernel_ms", "ongym_query_occupancy", "ongym_query_occupancy_policy",
-    "ongym_query_link_weight_entry", "ongym_last_error", "ongym_abi_version", "ongym_sizeof")
+    "ongym_query_link_weight_entry", "ongym_query_path_rows", "ongym_last_error", "ongym_abi_version", "ongym_sizeof")
 
 
 def load_library(path: Optional[str] = None):

@@ -943,6 +943,15 @@ class BatchedQRMSAEnv:
             return None
         return dict(mult=int(out[1]), index=int(out[2]), bits=int(out[3]), w1=float(entry[0]), w2=float(entry[1]))
 
+    def path_rows(self, path: int) -> dict:
+        """Route `path` as first fit's copy of the route records spells it out (ongym_query_path_rows): dict(hops, links (the
+        four link fields), long (the route takes the link loop; its fields are 0), word (the dword as it lies in device memory))."""
+        out = C.c_uint32(0)
+        self._check(self.lib.ongym_query_path_rows(self._h, int(path), C.byref(out)), "ongym_query_path_rows")
+        w = out.value
+        return dict(hops=w & 0xFF, links=[(w >> (8 + 6 * r)) & 0x1F for r in range(4)],
+                    long=bool(w >> 31), word=w)
+
     # ---- save / restore / fork replica states (ongym_state_*, ongym_fork; include/ongym.h) -----------------------------
     # A replica's state is its network, running services, clock, pending request, request counter, stream key, parameters and
     # ongym_stats, except the total_* work counters, which stay with the destination.  Python-side counters are not device
