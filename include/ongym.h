@@ -503,6 +503,55 @@ int ongym_repair_links(ongym_env *env, const uint64_t *sets, int32_t per_replica
  * Read-only.  Refused (ONGYM_E_ARG): NULL failed_out.  Buffers and timing as ongym_cut_links'. */
 int ongym_failed_links(ongym_env *env, uint64_t *failed_out);
 
+/* Moves running lightpaths on LIVE replicas: a chosen record is placed again, at a chosen action or where first fit puts it
+ * (K = k_paths, M = n_mods, S = n_slots, C = capacity, N = n_moves).  A move is a restoration of ongym_cut_links with one victim
+ * and no failed link, written back to the victim's own record index.
+ * moves     int32 [batch][N][2] = (record, target).  A replica applies its moves in order; each sees the state the previous left.
+ *   record  an index in [0, active), or ONGYM_MOVE_TOP: the running record that no move of this call has attempted yet
+ *           (explicit ones included, whatever their outcome) and whose last slot, slot + n - 1, is highest; ties go to the
+ *           lowest index.  Indices are stable: a moved record keeps its index, its release time with its sign (the disrupted
+ *           flag) and its id, and no other record changes place, so an index read from the records before the call holds
+ *           during and after it.
+ *   target  a step action k M S + (M - 1 - m) S + start on the route list of the record's own node pair (the route's pair as
+ *           the restorations find it), or ONGYM_MOVE_FIRST_FIT.  The service keeps its capacity n mod_se[m]; under format m' it
+ *           takes ceil(n mod_se[m] / mod_se[m']) slots, the restorations' rule.
+ *   Width   a move writes no record wider than the lean step kernels of the environment can carry, because traffic goes on
+ *           after it: where a lean kernel may run (an eligible configuration whose traffic so far fits the lean tables), the
+ *           limit is the widest slot count of the traffic table (the rows of the pair table), 32 in the narrow build;
+ *           otherwise it is S.  A format under which the service would take more slots is "no spectrum" (status 3) for an
+ *           explicit target and is passed over by ONGYM_MOVE_FIRST_FIT.
+ * One move: 1. the record's own range counts as free (n + 1 slots, clamped at S) and the record is no interferer, nor, with id
+ *   tracking, are its namesakes; 2. an explicit target must be one of `_get_candidates`' starts for the new slot count on the
+ *   target route in that state (n' free slots and the guard slot unless the range ends at S), so a failed link is never chosen
+ *   and a target that overlaps the old range is fine; 3. the target must pass the step's admission test with the replica's margin
+ *   (the exact ASE lower bound where first fit uses it, then the GN model); 4. ONGYM_MOVE_FIRST_FIT is first fit's search - routes
+ *   in order, formats best first, the lowest start - over the pair's routes, with ONGYM_MOVE_OWN_ROUTE over the record's own
+ *   route only; 5. a result equal to the present placement changes nothing; 6. on success the old range is released, the new one
+ *   provisioned with its guard slot, the record words rewritten in place, and under id tracking Service.OSNR becomes the new
+ *   GSNR and episode_osnr_sum moves by new - old; 7. on any failure the replica is exactly as before that move.
+ *   No statistic other than episode_osnr_sum (with ids) changes, total_* included; the pending request, the clock, the stream
+ *   position and the move log stay.  A replica none of whose moves succeeds is left byte for byte as it was.
+ * move_out  float64 [batch][N][6]:
+ *             0 status           0 moved; 1 invalid: record out of [0, active), no record left for ONGYM_MOVE_TOP, action out of
+ *                                [0, K M S), or the pair has no route k; 2 unchanged: the target is the present placement;
+ *                                3 no spectrum: n' above the width limit, the start is no candidate start, or first fit found no
+ *                                start anywhere;
+ *                                4 refused on QoT
+ *             1 record           the resolved index, -1 if none
+ *             2 old_action       the present placement in the encoding above, with the record's k on its pair's list (-1 with
+ *                                column 1)
+ *             3 new_action       the placement after the move: column 2 unless moved
+ *             4 margin           GSNR - threshold - margin of the new placement in dB, NaN unless moved
+ *             5 slot_hops_delta  n' hops' - n hops, 0 unless moved
+ * Refused (ONGYM_E_ARG): NULL moves, NULL move_out, n_moves < 1, unknown flags, n_mods_consider < n_mods, pair lists that
+ * disagree on a route's node pair; ONGYM_E_LIMIT: the LDS block (the state block + C / 8 bytes) exceeds 160 KiB.
+ * Buffers: host buffers (staged; the call synchronises), or device buffers with cfg.io_device (the call only launches on the
+ * environment's stream and nothing synchronises).  ongym_last_kernel_ms times the kernel. */
+enum { ONGYM_MOVE_TOP = -1 };        /* record selector */
+enum { ONGYM_MOVE_FIRST_FIT = -1 };  /* target selector */
+enum { ONGYM_MOVE_OWN_ROUTE = 1 };   /* flag */
+int ongym_move_services(ongym_env *env, int32_t n_moves, const int32_t *moves, int32_t flags, double *move_out);
+
 /* What the network could still carry right now: per replica and per candidate action of a list, first fit's admission decision
  * for EVERY request the traffic model can draw - every unordered node pair and every bit rate of a list - on the replica's
  * current state (N = n_nodes, K = k_paths, M = n_mods, S = n_slots, C = capacity, Q = N (N - 1) / 2, A = n_actions, R = n_rates).

@@ -30,6 +30,7 @@
 #include "ongym_impact.hpp"        // effect of candidate actions on the running lightpaths (ongym_action_impact)
 #include "ongym_failure.hpp"       // link failures and first-fit restoration (ongym_failure_impact, ongym_failure_sets)
 #include "ongym_cut.hpp"           // link failures on live replicas (ongym_cut_links, ongym_repair_links, ongym_failed_links)
+#include "ongym_move.hpp"          // running lightpaths moved on live replicas (ongym_move_services)
 #include "ongym_admission.hpp"     // first-fit admission of every node pair and bit rate (ongym_admission_map)
 #include "ongym_playout.hpp"       // candidate actions followed by H policy steps on a private copy (ongym_playout)
 
@@ -1538,6 +1539,34 @@ int ongym_failed_links(ongym_env *env, uint64_t *failed_out) {
     rc = timed_launch(env, [&] {
         return with_layout(P, [&](auto, auto R32) {     // the stored record codec
             return launch_lds(env, k_failed_links<R32>, dim3(P.batch), 0, env->d_P, sp[0].as<uint64_t>());
+        });
+    });
+    return rc ? rc : stage_close(env, sp);
+}
+
+int ongym_move_services(ongym_env *env, int32_t n_moves, const int32_t *moves, int32_t flags, double *move_out) {
+    if (!env) return ONGYM_E_ARG;
+    if (!moves || !move_out) return fail_arg(env, "null moves/move_out");
+    if (n_moves < 1) return fail_arg(env, "n_moves must be at least 1");
+    if (flags & ~ONGYM_MOVE_OWN_ROUTE) return fail_arg(env, "unknown flags: only ONGYM_MOVE_OWN_ROUTE is defined");
+    if (int rc = cut_refusals(env)) return rc;
+    const Params &P = env->P;
+    // the widest record a move may write: a lean step kernel may run on this environment later, and it carries no slot count
+    // above its pair table's rows and, in the narrow build, above 32 (ongym_fast.hpp, "Eligibility")
+    const int max_slots = (env->fast_ok && !env->trace_used) ? std::min(P.tab_nmax, env->fast_wide ? 512 : 32) : P.n_slots;
+    const size_t lds = move_lds_bytes(P);
+    if (lds > 160 * 1024) return fail_arg(env, "the move kernel's LDS block exceeds 160 KiB: lower capacity", ONGYM_E_LIMIT);
+    HIP_TRY(env, hipSetDevice(env->cfg.device));
+    const size_t B = (size_t)P.batch, N = (size_t)n_moves;
+    Span sp[] = {{move_out, B * N * kMoveOut * sizeof(double), kOut}, {moves, B * N * 2 * sizeof(int32_t), kIn}};   // staging: move_out | moves
+    int rc;
+    if ((rc = stage_open(env, env->stage[kStageMove], sp))) return rc;
+    rc = timed_launch(env, [&] {
+        return with_layout(P, [&](auto UA, auto R32) {     // attenuation and the stored record codec
+            return launch_lds(env, k_move_services<UA, R32>, dim3(P.batch), lds, env->d_P, (int)n_moves,
+                              sp[1].as<const int32_t>(), (int)((flags & ONGYM_MOVE_OWN_ROUTE) != 0), std::min(max_slots, P.n_slots),
+                              env->d_path_pair,
+                              sp[0].as<double>());
         });
     });
     return rc ? rc : stage_close(env, sp);

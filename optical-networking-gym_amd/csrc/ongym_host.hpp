@@ -25,6 +25,7 @@ enum {
     kStageMask,     // ongym_observe (mask | obs) and ongym_sample_actions (mask | actions): ONE buffer for the action mask
     kStageReset,    // ongym_reset, _reset_episode_counters: the mask; these two return without synchronising
     kStageQuery,    // the ongym_query_* calls: used with io_device too (query results are always host buffers)
+    kStageMove,     // ongym_move_services: move_out | moves
     kStages
 };
 

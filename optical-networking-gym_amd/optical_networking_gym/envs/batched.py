@@ -658,6 +658,68 @@ class BatchedQRMSAEnv:
         self._check(self.lib.ongym_failed_links(self._h, f.ctypes.data), "ongym_failed_links")
         return f
 
+    # ---- running lightpaths moved on live replicas (ongym_move_services, include/ongym.h) -----------------------------------
+    def move_services(self, moves, own_route=False, out=None):
+        """Move running lightpaths on every replica ITSELF: float64 [B, N, 6], columns nat.MOVE_COLUMNS.  moves is int32
+        [B, N, 2] or [N, 2] (one list for every replica), rows (record, target), applied in order, each on the state the
+        previous one left.  record: an index of services(), or nat.MOVE_TOP = the record no move of this call has attempted
+        whose last slot is highest (ties: the lowest index).  target: a step action k M S + (M - 1 - m) S + start on the
+        routes of the record's own node pair, or nat.MOVE_FIRST_FIT = where first fit places the service with its own spectrum
+        counted as free (own_route=True: on its present route only).  The service keeps its capacity, so another format
+        changes its slot count.  A target is taken only if its start is a candidate start of that state and it passes the
+        step's QoT test with the replica's margin; otherwise the replica is exactly as before that move (status 1 invalid,
+        2 unchanged, 3 no spectrum, 4 QoT).  A moved record keeps its index, release time and id; no statistic changes
+        (with ids, episode_osnr_sum follows Service.OSNR).  A host environment takes and returns numpy arrays.  An io_device
+        environment takes a contiguous torch.int32 tensor of shape (B, N, 2) on its device and writes into `out`, a float64
+        tensor of shape (B, N, 6), on torch's current stream (env.set_stream), without synchronising."""
+        c = self.holder.struct
+        B = self.batch_size
+        if c.n_mods_consider < c.n_mods:
+            raise ValueError("move_services searches every format: it needs modulations_to_consider == the number of modulations")
+        ncol = len(nat.MOVE_COLUMNS)
+        flags = nat.MOVE_OWN_ROUTE if own_route else 0
+        if c.io_device:
+            import torch
+            from .. import rl
+            dev = rl._device(self)
+            if not isinstance(moves, torch.Tensor) or moves.dtype != torch.int32 or moves.device != dev:
+                raise ValueError(f"moves must be a torch.int32 tensor on {dev}")
+            if moves.dim() != 3 or moves.shape[0] != B or moves.shape[1] < 1 or moves.shape[2] != 2 or not moves.is_contiguous():
+                raise ValueError(f"moves must be contiguous with shape ({B}, N, 2), N >= 1")
+            N = int(moves.shape[1])
+            if out is None:
+                raise ValueError(f"an io_device environment needs out, a float64 tensor of shape ({B}, N, {ncol})")
+            self._check_tensor(out, "out", torch.float64, (B, N, ncol), dev)
+            rl._check_stream(self)
+            self._check(self.lib.ongym_move_services(self._h, N, C.c_void_p(moves.data_ptr()), flags, C.c_void_p(out.data_ptr())),
+                        "ongym_move_services")
+            return out
+        if out is not None:
+            raise ValueError("out is for io_device environments; a host environment returns a new array")
+        if not isinstance(moves, np.ndarray) or moves.dtype != np.int32:
+            raise ValueError("moves must be a numpy int32 array")
+        if moves.ndim == 2:
+            moves = np.broadcast_to(moves[None], (B,) + moves.shape)
+        if moves.ndim != 3 or moves.shape[0] != B or moves.shape[1] < 1 or moves.shape[2] != 2:
+            raise ValueError(f"moves must have shape (N, 2) or ({B}, N, 2), N >= 1")
+        moves = np.ascontiguousarray(moves)
+        N = moves.shape[1]
+        res = np.zeros((B, N, ncol), np.float64)
+        self._check(self.lib.ongym_move_services(self._h, N, moves.ctypes.data, flags, res.ctypes.data), "ongym_move_services")
+        return res
+
+    def defragment(self, n, own_route=True):
+        """The classic sweep "highest service to first fit", n times per replica: move_services with n rows
+        (nat.MOVE_TOP, nat.MOVE_FIRST_FIT).  Every move takes the record not yet attempted whose last slot is highest and
+        places it where first fit would (own_route=True: on its present route).  Returns move_services' array.  A host
+        environment only; an io_device environment calls move_services with its own tensors."""
+        if self.holder.struct.io_device:
+            raise ValueError("defragment builds a host move list: an io_device environment calls move_services")
+        if int(n) < 1:
+            raise ValueError("n must be at least 1")
+        moves = np.tile(np.array([nat.MOVE_TOP, nat.MOVE_FIRST_FIT], np.int32), (int(n), 1))
+        return self.move_services(moves, own_route=own_route)
+
     # ---- first-fit admission of every node pair and bit rate (ongym_admission_map, include/ongym.h) ------------------------
     @property
     def admission_pairs(self) -> np.ndarray:
