@@ -17,6 +17,7 @@ import numpy as np
 
 from .. import _native as nat
 from .._tables import StaticTables
+from ._io import io_for
 
 
 class OngymError(RuntimeError):
@@ -83,6 +84,24 @@ class BatchedQRMSAEnv:
             raise ValueError(f"{name} must be a contiguous {what or f'{dtype} tensor of shape {shape}'} on {dev}")
         if t.data_ptr() % (align or t.element_size()):
             raise ValueError(f"{name} must be {f'{align}-byte aligned' if align else 'aligned to its element size'}")
+
+    def _needs_every_format(self, who: str):
+        """The refusal of a format window by a call that searches all formats; `who` leads the sentence in"""
+        c = self.holder.struct
+        if c.n_mods_consider < c.n_mods:
+            raise ValueError(f"{who} every format: it needs modulations_to_consider == the number of modulations")
+
+    def _actions(self, io, actions, required=False, samples=None):
+        """(actions as the library takes them, A) of candidate step actions: int32 [B, A] or [B] (A = 1), 1 <= A <=
+        nat.MAX_IMPACT_ACTIONS; None, unless `required`: no array, A = 1.  samples: playout's R, which bounds A R."""
+        B, A = self.batch_size, 1
+        if actions is not None or required:
+            actions, A = io.array(actions, "actions", np.int32, [(B, None)], f"({B}, A) or ({B},)", column=True)
+        if not 1 <= A <= nat.MAX_IMPACT_ACTIONS:
+            raise ValueError(f"the number of actions per replica must lie in [1, {nat.MAX_IMPACT_ACTIONS}]")
+        if samples is not None and A * samples > nat.MAX_PLAYOUT_SCENARIOS:
+            raise ValueError(f"actions x samples per replica must not exceed {nat.MAX_PLAYOUT_SCENARIOS}")
+        return actions, A
 
     @property
     def reject_action(self) -> int:
@@ -207,27 +226,11 @@ class BatchedQRMSAEnv:
         if not 1 <= J <= nat.MAX_BLOCKS:
             raise ValueError(f"blocks must lie in [1, {nat.MAX_BLOCKS}]")
         B, n = self.batch_size, self.holder.struct.k_paths * J + 1
-        shapes = ((B, self.block_obs_dim(J)), (B, n), (B, n))
-        if self.holder.struct.io_device:
-            import torch
-            from .. import rl
-            if out is None:
-                raise ValueError("an io_device environment needs out=(obs, mask, action_map) tensors")
-            if not isinstance(out, (tuple, list)) or len(out) != 3:
-                raise ValueError("out must be a tuple (obs, mask, action_map)")
-            dev = rl._device(self)
-            for t, name, dt, shape in zip(out, ("obs", "mask", "action_map"), (torch.float32, torch.uint8, torch.int32), shapes):
-                self._check_tensor(t, name, dt, shape, dev, align=4)
-            rl._check_stream(self)
-            self._check(self.lib.ongym_observe_blocks(self._h, J, *(C.c_void_p(t.data_ptr()) for t in out)),
-                        "ongym_observe_blocks")
-            return tuple(out)
-        if out is not None:
-            raise ValueError("out is for io_device environments; a host environment returns new arrays")
-        obs, mask, amap = np.zeros(shapes[0], np.float32), np.zeros(shapes[1], np.uint8), np.zeros(shapes[2], np.int32)
-        self._check(self.lib.ongym_observe_blocks(self._h, J, obs.ctypes.data, mask.ctypes.data, amap.ctypes.data),
-                    "ongym_observe_blocks")
-        return obs, mask, amap
+        io = io_for(self)
+        (obs, mask, amap), ret = io.outputs(out, [("obs", np.float32, (B, self.block_obs_dim(J))), ("mask", np.uint8, (B, n)),
+                                                  ("action_map", np.int32, (B, n))], align=4)
+        io.call("ongym_observe_blocks", J, io.ptr(obs), io.ptr(mask), io.ptr(amap))
+        return ret
 
     @staticmethod
     def decode_block_actions(block_actions, action_map):
@@ -253,37 +256,13 @@ class BatchedQRMSAEnv:
         _update_link_stats does for every link at each replica's current time.  Read-only.  A host environment returns numpy
         arrays (link_stats: a C-contiguous numpy array).  An io_device environment writes into `out` = (link, compactness) and
         link_stats, torch tensors on its device, on torch's current stream (env.set_stream), without synchronising."""
-        c = self.holder.struct
-        B, E = self.batch_size, c.n_links
-        shapes = ((B, E, len(nat.LINK_METRICS)), (B,), (B, E, len(nat.LINK_STATS)))
-        if c.io_device:
-            import torch
-            from .. import rl
-            if out is None:
-                raise ValueError("an io_device environment needs out=(link, compactness) tensors")
-            if not isinstance(out, (tuple, list)) or len(out) != 2:
-                raise ValueError("out must be a tuple (link, compactness)")
-            dev = rl._device(self)
-            named = list(zip(out, ("link", "compactness"), (torch.float32, torch.float64), shapes[:2]))
-            if link_stats is not None:
-                named.append((link_stats, "link_stats", torch.float64, shapes[2]))
-            for t, name, dt, shape in named:
-                self._check_tensor(t, name, dt, shape, dev)
-            rl._check_stream(self)
-            ptrs = [C.c_void_p(t.data_ptr()) for t in out] + [C.c_void_p(link_stats.data_ptr() if link_stats is not None else None)]
-            self._check(self.lib.ongym_link_metrics(self._h, *ptrs), "ongym_link_metrics")
-            return tuple(out)
-        if out is not None:
-            raise ValueError("out is for io_device environments; a host environment returns new arrays")
-        if link_stats is not None:
-            if (not isinstance(link_stats, np.ndarray) or link_stats.dtype != np.float64 or link_stats.shape != shapes[2]
-                    or not link_stats.flags.c_contiguous or not link_stats.flags.writeable):
-                raise ValueError(f"link_stats must be a writeable C-contiguous float64 numpy array of shape {shapes[2]}")
-        link, comp = np.zeros(shapes[0], np.float32), np.zeros(shapes[1], np.float64)
-        self._check(self.lib.ongym_link_metrics(self._h, link.ctypes.data, comp.ctypes.data,
-                                                link_stats.ctypes.data if link_stats is not None else None),
-                    "ongym_link_metrics")
-        return link, comp
+        B, E = self.batch_size, self.holder.struct.n_links
+        io = io_for(self)
+        (link, comp), ret = io.outputs(out, [("link", np.float32, (B, E, len(nat.LINK_METRICS))),
+                                             ("compactness", np.float64, (B,))])
+        link_stats = io.fixed(link_stats, "link_stats", np.float64, (B, E, len(nat.LINK_STATS)), inplace=True)
+        io.call("ongym_link_metrics", io.ptr(link), io.ptr(comp), io.ptr(link_stats))
+        return ret
 
     # ---- QoT of the running lightpaths (ongym_service_qot, include/ongym.h) ------------------------------------------------
     def service_qot(self, out=None):
@@ -295,30 +274,12 @@ class BatchedQRMSAEnv:
         on torch's current stream (env.set_stream), without synchronising."""
         c = self.holder.struct
         B = self.batch_size
-        shapes = ((B, c.capacity, len(nat.SERVICE_QOT)), (B, len(nat.REPLICA_QOT)), (B, c.n_links, len(nat.LINK_QOT)))
-        if c.io_device:
-            import torch
-            from .. import rl
-            if out is None:
-                raise ValueError("an io_device environment needs out=(svc, replica, link) tensors")
-            if not isinstance(out, (tuple, list)) or len(out) != 3:
-                raise ValueError("out must be a tuple (svc, replica, link)")
-            if all(t is None for t in out):
-                raise ValueError("out: at least one of svc, replica, link must be a tensor")
-            dev = rl._device(self)
-            for t, name, dt, shape in zip(out, ("svc", "replica", "link"), (torch.float64, torch.float64, torch.float32), shapes):
-                if t is not None:
-                    self._check_tensor(t, name, dt, shape, dev)
-            rl._check_stream(self)
-            ptrs = [C.c_void_p(t.data_ptr() if t is not None else None) for t in out]
-            self._check(self.lib.ongym_service_qot(self._h, *ptrs), "ongym_service_qot")
-            return tuple(out)
-        if out is not None:
-            raise ValueError("out is for io_device environments; a host environment returns new arrays")
-        svc, rep, link = np.zeros(shapes[0], np.float64), np.zeros(shapes[1], np.float64), np.zeros(shapes[2], np.float32)
-        self._check(self.lib.ongym_service_qot(self._h, svc.ctypes.data, rep.ctypes.data, link.ctypes.data),
-                    "ongym_service_qot")
-        return svc, rep, link
+        io = io_for(self)
+        (svc, rep, link), ret = io.outputs(out, [("svc", np.float64, (B, c.capacity, len(nat.SERVICE_QOT))),
+                                                 ("replica", np.float64, (B, len(nat.REPLICA_QOT))),
+                                                 ("link", np.float32, (B, c.n_links, len(nat.LINK_QOT)))], optional=True)
+        io.call("ongym_service_qot", io.ptr(svc), io.ptr(rep), io.ptr(link))
+        return ret
 
     # ---- effect of candidate actions on the running lightpaths (ongym_action_impact, include/ongym.h) -----------------------
     def action_impact(self, actions, svc=None, out=None):
@@ -328,55 +289,14 @@ class BatchedQRMSAEnv:
         1 <= A <= nat.MAX_IMPACT_ACTIONS.  svc: optionally the svc array of service_qot() on the same state, which saves the
         baseline pass.  Read-only.  A host environment takes and returns numpy arrays.  An io_device environment takes torch
         tensors on its device and writes into `out`, on torch's current stream (env.set_stream), without synchronising."""
-        c = self.holder.struct
         B = self.batch_size
-        svc_shape = (B, c.capacity, len(nat.SERVICE_QOT))
-        if c.io_device:
-            import torch
-            from .. import rl
-            dev = rl._device(self)
-            if not isinstance(actions, torch.Tensor) or actions.dtype != torch.int32 or actions.device != dev:
-                raise ValueError(f"actions must be a torch.int32 tensor on {dev}")
-            if actions.dim() == 1:
-                actions = actions.reshape(-1, 1)
-            if actions.dim() != 2 or actions.shape[0] != B or not actions.is_contiguous():
-                raise ValueError(f"actions must be contiguous with shape ({B}, A) or ({B},)")
-            A = int(actions.shape[1])
-            if not 1 <= A <= nat.MAX_IMPACT_ACTIONS:
-                raise ValueError(f"the number of actions per replica must lie in [1, {nat.MAX_IMPACT_ACTIONS}]")
-            if out is None:
-                raise ValueError("an io_device environment needs out, a float64 tensor of shape (B, A, 8)")
-            shape = (B, A, len(nat.ACTION_IMPACT))
-            for t, name, sh in ((out, "out", shape), (svc, "svc", svc_shape)):
-                if t is not None:
-                    self._check_tensor(t, name, torch.float64, sh, dev)
-            if actions.data_ptr() % 4:
-                raise ValueError("actions must be aligned to its element size")
-            rl._check_stream(self)
-            self._check(self.lib.ongym_action_impact(self._h, A, C.c_void_p(actions.data_ptr()),
-                                                     C.c_void_p(svc.data_ptr() if svc is not None else None),
-                                                     C.c_void_p(out.data_ptr())), "ongym_action_impact")
-            return out
-        if out is not None:
-            raise ValueError("out is for io_device environments; a host environment returns a new array")
-        if not isinstance(actions, np.ndarray) or actions.dtype != np.int32:
-            raise ValueError("actions must be a numpy int32 array")
-        if actions.ndim == 1:
-            actions = actions.reshape(-1, 1)
-        if actions.ndim != 2 or actions.shape[0] != B:
-            raise ValueError(f"actions must have shape ({B}, A) or ({B},)")
-        A = int(actions.shape[1])
-        if not 1 <= A <= nat.MAX_IMPACT_ACTIONS:
-            raise ValueError(f"the number of actions per replica must lie in [1, {nat.MAX_IMPACT_ACTIONS}]")
-        actions = np.ascontiguousarray(actions)
-        if svc is not None:
-            if not isinstance(svc, np.ndarray) or svc.dtype != np.float64 or svc.shape != svc_shape:
-                raise ValueError(f"svc must be a numpy float64 array of shape {svc_shape}")
-            svc = np.ascontiguousarray(svc)
-        res = np.zeros((B, A, len(nat.ACTION_IMPACT)), np.float64)
-        self._check(self.lib.ongym_action_impact(self._h, A, actions.ctypes.data, svc.ctypes.data if svc is not None else None,
-                                                 res.ctypes.data), "ongym_action_impact")
-        return res
+        io = io_for(self)
+        actions, A = self._actions(io, actions, required=True)
+        svc = io.fixed(svc, "svc", np.float64, (B, self.holder.struct.capacity, len(nat.SERVICE_QOT)))
+        (res,), ret = io.outputs(out, [("out", np.float64, (B, A, len(nat.ACTION_IMPACT)))],
+                                 "a float64 tensor of shape (B, A, 8)", detail=False)
+        io.call("ongym_action_impact", A, io.ptr(actions), io.ptr(svc), io.ptr(res))
+        return ret
 
     # ---- single-link failures and first-fit restoration (ongym_failure_impact, include/ongym.h) ----------------------------
     def failure_impact(self, links=None, out=None, detail=False):
@@ -390,59 +310,19 @@ class BatchedQRMSAEnv:
         tensor, or with detail the pair (link, svc)), on torch's current stream (env.set_stream), without synchronising."""
         c = self.holder.struct
         B, E = self.batch_size, c.n_links
-        if c.n_mods_consider < c.n_mods:
-            raise ValueError("failure_impact searches every format: it needs modulations_to_consider == the number of modulations")
-        ncol = len(nat.FAILURE_IMPACT)
-        if c.io_device:
-            import torch
-            from .. import rl
-            dev = rl._device(self)
-            F = E
-            if links is not None:
-                if not isinstance(links, torch.Tensor) or links.dtype != torch.int32 or links.device != dev:
-                    raise ValueError(f"links must be a torch.int32 tensor on {dev}")
-                if links.dim() == 1:
-                    links = links.reshape(-1, 1)
-                if links.dim() != 2 or links.shape[0] != B or not links.is_contiguous():
-                    raise ValueError(f"links must be contiguous with shape ({B}, F) or ({B},)")
-                F = int(links.shape[1])
-                if links.data_ptr() % 4:
-                    raise ValueError("links must be aligned to its element size")
-            if not 1 <= F <= E:
-                raise ValueError(f"the number of failed links per replica must lie in [1, {E}]")
-            if out is None:
-                raise ValueError("an io_device environment needs out, a float64 tensor of shape (B, F, 10) (detail: with an int32 "
-                                 "tensor of shape (B, F, C), as a pair)")
-            if detail and (not isinstance(out, (tuple, list)) or len(out) != 2):
-                raise ValueError("with detail, out must be the pair (link, svc)")
-            link_t, svc_t = out if detail else (out, None)
-            self._check_tensor(link_t, "out" if not detail else "out[0]", torch.float64, (B, F, ncol), dev)
-            if detail:
-                self._check_tensor(svc_t, "out[1]", torch.int32, (B, F, c.capacity), dev)
-            rl._check_stream(self)
-            self._check(self.lib.ongym_failure_impact(self._h, F, C.c_void_p(links.data_ptr() if links is not None else None),
-                                                      C.c_void_p(link_t.data_ptr()),
-                                                      C.c_void_p(svc_t.data_ptr() if detail else None)), "ongym_failure_impact")
-            return out
-        if out is not None:
-            raise ValueError("out is for io_device environments; a host environment returns new arrays")
+        self._needs_every_format("failure_impact searches")
+        io = io_for(self)
         F = E
         if links is not None:
-            if not isinstance(links, np.ndarray) or links.dtype != np.int32:
-                raise ValueError("links must be a numpy int32 array")
-            if links.ndim == 1:
-                links = links.reshape(-1, 1)
-            if links.ndim != 2 or links.shape[0] != B:
-                raise ValueError(f"links must have shape ({B}, F) or ({B},)")
-            F = int(links.shape[1])
-            links = np.ascontiguousarray(links)
+            links, F = io.array(links, "links", np.int32, [(B, None)], f"({B}, F) or ({B},)", column=True)
         if not 1 <= F <= E:
             raise ValueError(f"the number of failed links per replica must lie in [1, {E}]")
-        res = np.zeros((B, F, ncol), np.float64)
-        svc = np.zeros((B, F, c.capacity), np.int32) if detail else None
-        self._check(self.lib.ongym_failure_impact(self._h, F, links.ctypes.data if links is not None else None, res.ctypes.data,
-                                                  svc.ctypes.data if detail else None), "ongym_failure_impact")
-        return (res, svc) if detail else res
+        (res, svc), ret = io.outputs(out, [("link", np.float64, (B, F, len(nat.FAILURE_IMPACT))),
+                                           ("svc", np.int32, (B, F, c.capacity))],
+                                     "a float64 tensor of shape (B, F, 10) (detail: with an int32 tensor of shape (B, F, C), as a pair)",
+                                     detail=bool(detail))
+        io.call("ongym_failure_impact", F, io.ptr(links), io.ptr(res), io.ptr(svc))
+        return ret
 
     # ---- failures of link sets: dual cuts, nodes, shared-risk groups (ongym_failure_sets, include/ongym.h) ------------------
     @staticmethod
@@ -484,83 +364,36 @@ class BatchedQRMSAEnv:
         tensor, or with detail the pair (set, svc)), on torch's current stream (env.set_stream), without synchronising."""
         c = self.holder.struct
         B = self.batch_size
-        if c.n_mods_consider < c.n_mods:
-            raise ValueError("failure_sets searches every format: it needs modulations_to_consider == the number of modulations")
-        ncol = len(nat.FAILURE_SETS)
-        if c.io_device:
-            import torch
-            from .. import rl
-            dev = rl._device(self)
-            wide = (torch.int64,) + ((torch.uint64,) if hasattr(torch, "uint64") else ())
-            if not isinstance(sets, torch.Tensor) or sets.dtype not in wide or sets.device != dev:
-                raise ValueError(f"sets must be a torch.int64 or torch.uint64 tensor on {dev}")
-            if (sets.dim() not in (2, 3) or sets.shape[-1] != 2 or (sets.dim() == 3 and sets.shape[0] != B)
-                    or not sets.is_contiguous()):
-                raise ValueError(f"sets must be contiguous with shape (F, 2) or ({B}, F, 2)")
-            F = int(sets.shape[-2])
-            if not 1 <= F <= nat.MAX_FAILURE_SETS:
-                raise ValueError(f"the number of link sets per replica must lie in [1, {nat.MAX_FAILURE_SETS}]")
-            if sets.data_ptr() % 8:
-                raise ValueError("sets must be aligned to its element size")
-            if out is None:
-                raise ValueError("an io_device environment needs out, a float64 tensor of shape (B, F, 12) (detail: with an int32 "
-                                 "tensor of shape (B, F, C), as a pair)")
-            if detail and (not isinstance(out, (tuple, list)) or len(out) != 2):
-                raise ValueError("with detail, out must be the pair (set, svc)")
-            set_t, svc_t = out if detail else (out, None)
-            self._check_tensor(set_t, "out" if not detail else "out[0]", torch.float64, (B, F, ncol), dev)
-            if detail:
-                self._check_tensor(svc_t, "out[1]", torch.int32, (B, F, c.capacity), dev)
-            rl._check_stream(self)
-            self._check(self.lib.ongym_failure_sets(self._h, F, C.c_void_p(sets.data_ptr()), int(sets.dim() == 3),
-                                                    C.c_void_p(set_t.data_ptr()),
-                                                    C.c_void_p(svc_t.data_ptr() if detail else None)), "ongym_failure_sets")
-            return out
-        if out is not None:
-            raise ValueError("out is for io_device environments; a host environment returns new arrays")
-        if isinstance(sets, (list, tuple)):
-            sets = self.pack_link_sets(sets, c.n_links)
-        if not isinstance(sets, np.ndarray) or sets.dtype != np.uint64:
-            raise ValueError("sets must be a numpy uint64 array or a list of link-index iterables")
-        if sets.ndim not in (2, 3) or sets.shape[-1] != 2 or (sets.ndim == 3 and sets.shape[0] != B):
-            raise ValueError(f"sets must have shape (F, 2) or ({B}, F, 2)")
-        F = int(sets.shape[-2])
+        self._needs_every_format("failure_sets searches")
+        io = io_for(self)
+        sets, F = io.array(sets, "sets", np.uint64, [(None, 2), (B, None, 2)], f"(F, 2) or ({B}, F, 2)",
+                           host_too=(lambda s: self.pack_link_sets(s, c.n_links) if isinstance(s, (list, tuple)) else s,
+                                      " or a list of link-index iterables", ""))
         if not 1 <= F <= nat.MAX_FAILURE_SETS:
             raise ValueError(f"the number of link sets per replica must lie in [1, {nat.MAX_FAILURE_SETS}]")
-        sets = np.ascontiguousarray(sets)
-        res = np.zeros((B, F, ncol), np.float64)
-        svc = np.zeros((B, F, c.capacity), np.int32) if detail else None
-        self._check(self.lib.ongym_failure_sets(self._h, F, sets.ctypes.data, int(sets.ndim == 3), res.ctypes.data,
-                                                svc.ctypes.data if detail else None), "ongym_failure_sets")
-        return (res, svc) if detail else res
+        (res, svc), ret = io.outputs(out, [("set", np.float64, (B, F, len(nat.FAILURE_SETS))),
+                                           ("svc", np.int32, (B, F, c.capacity))],
+                                     "a float64 tensor of shape (B, F, 12) (detail: with an int32 tensor of shape (B, F, C), as a pair)",
+                                     detail=bool(detail))
+        io.call("ongym_failure_sets", F, io.ptr(sets), int(sets.ndim == 3), io.ptr(res), io.ptr(svc))
+        return ret
 
     # ---- link failures on live replicas (ongym_cut_links, ongym_repair_links, ongym_failed_links, include/ongym.h) ----------
-    def _one_set_per_replica(self, sets, what: str):
+    def _one_set_per_replica(self, io, sets, what: str):
         """(sets as the library takes them, per_replica) for one link set per replica: uint64 [2] (shared) or [B, 2], or B
         link-index iterables (pack_link_sets); on an io_device environment a torch.int64 / torch.uint64 tensor on its device"""
-        c = self.holder.struct
         B = self.batch_size
-        if c.io_device:
-            import torch
-            from .. import rl
-            dev = rl._device(self)
-            wide = (torch.int64,) + ((torch.uint64,) if hasattr(torch, "uint64") else ())
-            if not isinstance(sets, torch.Tensor) or sets.dtype not in wide or sets.device != dev:
-                raise ValueError(f"sets must be a torch.int64 or torch.uint64 tensor on {dev}")
-            if tuple(sets.shape) not in ((2,), (B, 2)) or not sets.is_contiguous():
-                raise ValueError(f"sets must be contiguous with shape (2,) or ({B}, 2)")
-            if sets.data_ptr() % 8:
-                raise ValueError("sets must be aligned to its element size")
-            return sets, int(sets.dim() == 2)
-        if isinstance(sets, (list, tuple)):
-            if len(sets) != B:
+
+        def packed(s):
+            if not isinstance(s, (list, tuple)):
+                return s
+            if len(s) != B:
                 raise ValueError(f"{what} takes one link-index iterable per replica ({B})")
-            sets = self.pack_link_sets(sets, c.n_links)
-        if not isinstance(sets, np.ndarray) or sets.dtype != np.uint64:
-            raise ValueError("sets must be a numpy uint64 array or a list of link-index iterables, one per replica")
-        if sets.shape not in ((2,), (B, 2)):
-            raise ValueError(f"sets must have shape (2,) or ({B}, 2)")
-        return np.ascontiguousarray(sets), int(sets.ndim == 2)
+            return self.pack_link_sets(s, self.holder.struct.n_links)
+
+        sets, _ = io.array(sets, "sets", np.uint64, [(2,), (B, 2)], f"(2,) or ({B}, 2)",
+                           host_too=(packed, " or a list of link-index iterables, one per replica", ""))
+        return sets, int(sets.ndim == 2)
 
     def cut_links(self, sets, restore=True, out=None, detail=False):
         """Fail a set of links on every replica ITSELF (failure_sets only asks "what if"): float64 [B, 13], columns
@@ -579,84 +412,34 @@ class BatchedQRMSAEnv:
         index)), on torch's current stream (env.set_stream), without synchronising."""
         c = self.holder.struct
         B = self.batch_size
-        if c.n_mods_consider < c.n_mods:
-            raise ValueError("cut_links searches every format: it needs modulations_to_consider == the number of modulations")
-        ncol = len(nat.CUT_LINKS)
-        flags = 0 if restore else nat.CUT_NO_RESTORE
-        if c.io_device:
-            import torch
-            from .. import rl
-            sets, per = self._one_set_per_replica(sets, "cut_links")
-            dev = rl._device(self)
-            if out is None:
-                raise ValueError("an io_device environment needs out, a float64 tensor of shape (B, 13) (detail: with two int32 "
-                                 "tensors of shape (B, C), as a triple)")
-            if detail and (not isinstance(out, (tuple, list)) or len(out) != 3):
-                raise ValueError("with detail, out must be the triple (cut, svc, index)")
-            cut_t, svc_t, idx_t = out if detail else (out, None, None)
-            self._check_tensor(cut_t, "out" if not detail else "out[0]", torch.float64, (B, ncol), dev)
-            if detail:
-                self._check_tensor(svc_t, "out[1]", torch.int32, (B, c.capacity), dev)
-                self._check_tensor(idx_t, "out[2]", torch.int32, (B, c.capacity), dev)
-            rl._check_stream(self)
-            self._check(self.lib.ongym_cut_links(self._h, C.c_void_p(sets.data_ptr()), per, flags, C.c_void_p(cut_t.data_ptr()),
-                                                 C.c_void_p(svc_t.data_ptr() if detail else None),
-                                                 C.c_void_p(idx_t.data_ptr() if detail else None)), "ongym_cut_links")
-            return out
-        if out is not None:
-            raise ValueError("out is for io_device environments; a host environment returns new arrays")
-        sets, per = self._one_set_per_replica(sets, "cut_links")
-        res = np.zeros((B, ncol), np.float64)
-        svc = np.zeros((B, c.capacity), np.int32) if detail else None
-        idx = np.zeros((B, c.capacity), np.int32) if detail else None
-        self._check(self.lib.ongym_cut_links(self._h, sets.ctypes.data, per, flags, res.ctypes.data,
-                                             svc.ctypes.data if detail else None, idx.ctypes.data if detail else None),
-                    "ongym_cut_links")
-        return (res, (svc, idx)) if detail else res
+        self._needs_every_format("cut_links searches")
+        io = io_for(self)
+        sets, per = self._one_set_per_replica(io, sets, "cut_links")
+        (res, svc, idx), ret = io.outputs(out, [("cut", np.float64, (B, len(nat.CUT_LINKS))), ("svc", np.int32, (B, c.capacity)),
+                                                ("index", np.int32, (B, c.capacity))],
+                                          "a float64 tensor of shape (B, 13) (detail: with two int32 tensors of shape (B, C), as a triple)",
+                                          detail=bool(detail), host_form=lambda a: (a[0], (a[1], a[2])))
+        io.call("ongym_cut_links", io.ptr(sets), per, 0 if restore else nat.CUT_NO_RESTORE, io.ptr(res), io.ptr(svc), io.ptr(idx))
+        return ret
 
     def repair_links(self, sets, out=None):
         """Return fibre: the links of each replica's set that are failed (cut_links) get their spectrum back, entirely free;
         healthy links of the set are ignored.  int32 [B], the links returned per replica.  sets as cut_links'.  An io_device
         environment writes into `out`, an int32 tensor of shape (B,), on torch's current stream, without synchronising."""
-        B = self.batch_size
-        sets, per = self._one_set_per_replica(sets, "repair_links")
-        if self.holder.struct.io_device:
-            import torch
-            from .. import rl
-            if out is None:
-                raise ValueError("an io_device environment needs out, an int32 tensor of shape (B,)")
-            self._check_tensor(out, "out", torch.int32, (B,), rl._device(self))
-            rl._check_stream(self)
-            self._check(self.lib.ongym_repair_links(self._h, C.c_void_p(sets.data_ptr()), per, C.c_void_p(out.data_ptr())),
-                        "ongym_repair_links")
-            return out
-        if out is not None:
-            raise ValueError("out is for io_device environments; a host environment returns a new array")
-        n = np.zeros(B, np.int32)
-        self._check(self.lib.ongym_repair_links(self._h, sets.ctypes.data, per, n.ctypes.data), "ongym_repair_links")
-        return n
+        io = io_for(self)
+        sets, per = self._one_set_per_replica(io, sets, "repair_links")
+        (n,), ret = io.outputs(out, [("out", np.int32, (self.batch_size,))], "an int32 tensor of shape (B,)", detail=False)
+        io.call("ongym_repair_links", io.ptr(sets), per, io.ptr(n))
+        return ret
 
     def failed_links(self, out=None):
         """uint64 [B, 2]: the failed links of every replica, bit e & 63 of word e >> 6 for link e (pack_link_sets' order).
         Link e is failed exactly when its row has no free slot and no running record crosses it.  Read-only.  An io_device
         environment writes into `out`, a torch.int64 or torch.uint64 tensor of shape (B, 2), on torch's current stream."""
-        B = self.batch_size
-        if self.holder.struct.io_device:
-            import torch
-            from .. import rl
-            dev = rl._device(self)
-            wide = (torch.int64,) + ((torch.uint64,) if hasattr(torch, "uint64") else ())
-            if (not isinstance(out, torch.Tensor) or out.dtype not in wide or out.device != dev or tuple(out.shape) != (B, 2)
-                    or not out.is_contiguous() or out.data_ptr() % 8):
-                raise ValueError(f"an io_device environment needs out, a contiguous torch.int64 or torch.uint64 tensor of shape ({B}, 2) on {dev}")
-            rl._check_stream(self)
-            self._check(self.lib.ongym_failed_links(self._h, C.c_void_p(out.data_ptr())), "ongym_failed_links")
-            return out
-        if out is not None:
-            raise ValueError("out is for io_device environments; a host environment returns a new array")
-        f = np.zeros((B, 2), np.uint64)
-        self._check(self.lib.ongym_failed_links(self._h, f.ctypes.data), "ongym_failed_links")
-        return f
+        io = io_for(self)
+        (f,), ret = io.outputs(out, [("out", np.uint64, (self.batch_size, 2))], detail=False)
+        io.call("ongym_failed_links", io.ptr(f))
+        return ret
 
     # ---- running lightpaths moved on live replicas (ongym_move_services, include/ongym.h) -----------------------------------
     def move_services(self, moves, own_route=False, out=None):
@@ -672,41 +455,16 @@ class BatchedQRMSAEnv:
         (with ids, episode_osnr_sum follows Service.OSNR).  A host environment takes and returns numpy arrays.  An io_device
         environment takes a contiguous torch.int32 tensor of shape (B, N, 2) on its device and writes into `out`, a float64
         tensor of shape (B, N, 6), on torch's current stream (env.set_stream), without synchronising."""
-        c = self.holder.struct
-        B = self.batch_size
-        if c.n_mods_consider < c.n_mods:
-            raise ValueError("move_services searches every format: it needs modulations_to_consider == the number of modulations")
-        ncol = len(nat.MOVE_COLUMNS)
-        flags = nat.MOVE_OWN_ROUTE if own_route else 0
-        if c.io_device:
-            import torch
-            from .. import rl
-            dev = rl._device(self)
-            if not isinstance(moves, torch.Tensor) or moves.dtype != torch.int32 or moves.device != dev:
-                raise ValueError(f"moves must be a torch.int32 tensor on {dev}")
-            if moves.dim() != 3 or moves.shape[0] != B or moves.shape[1] < 1 or moves.shape[2] != 2 or not moves.is_contiguous():
-                raise ValueError(f"moves must be contiguous with shape ({B}, N, 2), N >= 1")
-            N = int(moves.shape[1])
-            if out is None:
-                raise ValueError(f"an io_device environment needs out, a float64 tensor of shape ({B}, N, {ncol})")
-            self._check_tensor(out, "out", torch.float64, (B, N, ncol), dev)
-            rl._check_stream(self)
-            self._check(self.lib.ongym_move_services(self._h, N, C.c_void_p(moves.data_ptr()), flags, C.c_void_p(out.data_ptr())),
-                        "ongym_move_services")
-            return out
-        if out is not None:
-            raise ValueError("out is for io_device environments; a host environment returns a new array")
-        if not isinstance(moves, np.ndarray) or moves.dtype != np.int32:
-            raise ValueError("moves must be a numpy int32 array")
-        if moves.ndim == 2:
-            moves = np.broadcast_to(moves[None], (B,) + moves.shape)
-        if moves.ndim != 3 or moves.shape[0] != B or moves.shape[1] < 1 or moves.shape[2] != 2:
-            raise ValueError(f"moves must have shape (N, 2) or ({B}, N, 2), N >= 1")
-        moves = np.ascontiguousarray(moves)
-        N = moves.shape[1]
-        res = np.zeros((B, N, ncol), np.float64)
-        self._check(self.lib.ongym_move_services(self._h, N, moves.ctypes.data, flags, res.ctypes.data), "ongym_move_services")
-        return res
+        B, ncol = self.batch_size, len(nat.MOVE_COLUMNS)
+        self._needs_every_format("move_services searches")
+        io = io_for(self)
+        shared = lambda m: np.broadcast_to(m[None], (B,) + m.shape) if isinstance(m, np.ndarray) and m.ndim == 2 else m  # noqa: E731
+        moves, N = io.array(moves, "moves", np.int32, [(B, None, 2)], f"({B}, N, 2), N >= 1", min_free=1, align=False,
+                            host_too=(shared, "", "(N, 2) or "))
+        (res,), ret = io.outputs(out, [("out", np.float64, (B, N, ncol))], f"a float64 tensor of shape ({B}, N, {ncol})",
+                                 detail=False)
+        io.call("ongym_move_services", N, io.ptr(moves), nat.MOVE_OWN_ROUTE if own_route else 0, io.ptr(res))
+        return ret
 
     def defragment(self, n, own_route=True):
         """The classic sweep "highest service to first fit", n times per replica: move_services with n rows
@@ -756,8 +514,7 @@ class BatchedQRMSAEnv:
         c = self.holder.struct
         B, N = self.batch_size, c.n_nodes
         Q = N * (N - 1) // 2
-        if c.n_mods_consider < c.n_mods:
-            raise ValueError("admission_map searches every format: it needs modulations_to_consider == the number of modulations")
+        self._needs_every_format("admission_map searches")
         if rates is None:
             if c.bit_rate_mode != 0:
                 raise ValueError("rates=None needs discrete bit rates: pass rates")
@@ -771,79 +528,20 @@ class BatchedQRMSAEnv:
                 raise ValueError(f"the number of rates must lie in [1, {nat.MAX_ADMISSION_RATES}]")
             if not np.all(np.isfinite(rates_arr)) or not np.all(rates_arr > 0):
                 raise ValueError("every rate must be finite and positive")
-        if isinstance(weights, str):
-            if weights != "traffic":
-                raise ValueError('weights must be "traffic", an array of shape (Q, R) or None')
-            weights = self.admission_weights()
-            traffic = True
-        else:
-            traffic = False
-        ncol = len(nat.ADMISSION_MAP)
-        rates_p = rates_arr.ctypes.data if rates_arr is not None else None
-        if c.io_device:
-            import torch
-            from .. import rl
-            dev = rl._device(self)
-            A = 1
-            if actions is not None:
-                if not isinstance(actions, torch.Tensor) or actions.dtype != torch.int32 or actions.device != dev:
-                    raise ValueError(f"actions must be a torch.int32 tensor on {dev}")
-                if actions.dim() == 1:
-                    actions = actions.reshape(-1, 1)
-                if actions.dim() != 2 or actions.shape[0] != B or not actions.is_contiguous():
-                    raise ValueError(f"actions must be contiguous with shape ({B}, A) or ({B},)")
-                A = int(actions.shape[1])
-                if actions.data_ptr() % 4:
-                    raise ValueError("actions must be aligned to its element size")
-            if not 1 <= A <= nat.MAX_IMPACT_ACTIONS:
-                raise ValueError(f"the number of actions per replica must lie in [1, {nat.MAX_IMPACT_ACTIONS}]")
-            if traffic:                                     # the configuration's weights, uploaded once per device
-                if getattr(self, "_admission_w", None) is None or self._admission_w.device != dev:
-                    self._admission_w = torch.from_numpy(weights).to(dev)
-                weights = self._admission_w
-            if weights is not None:
-                self._check_tensor(weights, "weights", torch.float64, (Q, R), dev)
-            if out is None:
-                raise ValueError("an io_device environment needs out, a float64 tensor of shape (B, A, 8) (detail: with an int32 and "
-                                 "a float32 tensor of shape (B, A, Q, R), as a triple)")
-            if detail and (not isinstance(out, (tuple, list)) or len(out) != 3):
-                raise ValueError("with detail, out must be the triple (summary, map, margin)")
-            sum_t, map_t, mar_t = out if detail else (out, None, None)
-            self._check_tensor(sum_t, "out" if not detail else "out[0]", torch.float64, (B, A, ncol), dev)
-            if detail:
-                self._check_tensor(map_t, "out[1]", torch.int32, (B, A, Q, R), dev)
-                self._check_tensor(mar_t, "out[2]", torch.float32, (B, A, Q, R), dev)
-            rl._check_stream(self)
-            ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)      # noqa: E731
-            self._check(self.lib.ongym_admission_map(self._h, A, ptr(actions), R, rates_p, ptr(weights), ptr(sum_t), ptr(map_t),
-                                                     ptr(mar_t)), "ongym_admission_map")
-            return out
-        if out is not None:
-            raise ValueError("out is for io_device environments; a host environment returns new arrays")
-        A = 1
-        if actions is not None:
-            if not isinstance(actions, np.ndarray) or actions.dtype != np.int32:
-                raise ValueError("actions must be a numpy int32 array")
-            if actions.ndim == 1:
-                actions = actions.reshape(-1, 1)
-            if actions.ndim != 2 or actions.shape[0] != B:
-                raise ValueError(f"actions must have shape ({B}, A) or ({B},)")
-            A = int(actions.shape[1])
-            actions = np.ascontiguousarray(actions)
-        if not 1 <= A <= nat.MAX_IMPACT_ACTIONS:
-            raise ValueError(f"the number of actions per replica must lie in [1, {nat.MAX_IMPACT_ACTIONS}]")
-        if weights is not None:
-            if not isinstance(weights, np.ndarray) or weights.dtype != np.float64 or weights.shape != (Q, R):
-                raise ValueError(f"weights must be a numpy float64 array of shape ({Q}, {R})")
-            weights = np.ascontiguousarray(weights)
-        res = np.zeros((B, A, ncol), np.float64)
-        amap = np.zeros((B, A, Q, R), np.int32) if detail else None
-        mar = np.zeros((B, A, Q, R), np.float32) if detail else None
-        self._check(self.lib.ongym_admission_map(self._h, A, actions.ctypes.data if actions is not None else None, R, rates_p,
-                                                 weights.ctypes.data if weights is not None else None, res.ctypes.data,
-                                                 amap.ctypes.data if detail else None, mar.ctypes.data if detail else None),
-                    "ongym_admission_map")
-        return (res, amap, mar) if detail else res
+        if isinstance(weights, str) and weights != "traffic":
+            raise ValueError('weights must be "traffic", an array of shape (Q, R) or None')
+        io = io_for(self)
+        actions, A = self._actions(io, actions)
+        if isinstance(weights, str):                        # the configuration's weights, uploaded once per device
+            weights = io.constant(self.admission_weights(), "_admission_w")
+        weights = io.fixed(weights, "weights", np.float64, (Q, R))
+        (res, amap, mar), ret = io.outputs(out, [("summary", np.float64, (B, A, len(nat.ADMISSION_MAP))),
+                                                 ("map", np.int32, (B, A, Q, R)), ("margin", np.float32, (B, A, Q, R))],
+                                           "a float64 tensor of shape (B, A, 8) (detail: with an int32 and a float32 tensor of shape "
+                                           "(B, A, Q, R), as a triple)", detail=bool(detail))
+        io.call("ongym_admission_map", A, io.ptr(actions), R, rates_arr.ctypes.data if rates_arr is not None else None,
+                io.ptr(weights), io.ptr(res), io.ptr(amap), io.ptr(mar))
+        return ret
 
     # ---- playouts: candidate actions followed by H policy steps (ongym_playout, include/ongym.h) ------------------------------
     def playout(self, actions=None, horizon: int = 32, policy: int = nat.POLICY_FIRST_FIT, samples: int = 1, seed: int = 0,
@@ -859,11 +557,9 @@ class BatchedQRMSAEnv:
         future; samples must be 1, seed is ignored).  Read-only.  A host environment takes and returns numpy arrays.  An
         io_device environment takes a torch tensor on its device and writes into `out`, on torch's current stream
         (env.set_stream), without synchronising."""
-        c = self.holder.struct
         B = self.batch_size
         H, R, policy = int(horizon), int(samples), int(policy)
-        if c.n_mods_consider < c.n_mods:
-            raise ValueError("playout's policies search every format: it needs modulations_to_consider == the number of modulations")
+        self._needs_every_format("playout's policies search")
         if not 1 <= H <= nat.MAX_PLAYOUT_HORIZON:
             raise ValueError(f"horizon must lie in [1, {nat.MAX_PLAYOUT_HORIZON}]")
         if not 1 <= R <= nat.MAX_PLAYOUT_SAMPLES:
@@ -873,53 +569,12 @@ class BatchedQRMSAEnv:
         flags = nat.PLAYOUT_OWN_STREAM if own_stream else 0
         seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         ncol = len(nat.PLAYOUT)
-
-        def check_A(A):
-            if not 1 <= A <= nat.MAX_IMPACT_ACTIONS:
-                raise ValueError(f"the number of actions per replica must lie in [1, {nat.MAX_IMPACT_ACTIONS}]")
-            if A * R > nat.MAX_PLAYOUT_SCENARIOS:
-                raise ValueError(f"actions x samples per replica must not exceed {nat.MAX_PLAYOUT_SCENARIOS}")
-
-        if c.io_device:
-            import torch
-            from .. import rl
-            dev = rl._device(self)
-            A = 1
-            if actions is not None:
-                if not isinstance(actions, torch.Tensor) or actions.dtype != torch.int32 or actions.device != dev:
-                    raise ValueError(f"actions must be a torch.int32 tensor on {dev}")
-                if actions.dim() == 1:
-                    actions = actions.reshape(-1, 1)
-                if actions.dim() != 2 or actions.shape[0] != B or not actions.is_contiguous():
-                    raise ValueError(f"actions must be contiguous with shape ({B}, A) or ({B},)")
-                A = int(actions.shape[1])
-                if actions.data_ptr() % 4:
-                    raise ValueError("actions must be aligned to its element size")
-            check_A(A)
-            if out is None:
-                raise ValueError(f"an io_device environment needs out, a float64 tensor of shape (B, A, R, {ncol})")
-            self._check_tensor(out, "out", torch.float64, (B, A, R, ncol), dev)
-            rl._check_stream(self)
-            self._check(self.lib.ongym_playout(self._h, A, C.c_void_p(actions.data_ptr() if actions is not None else None), H,
-                                               policy, R, C.c_uint64(seed), flags, C.c_void_p(out.data_ptr())), "ongym_playout")
-            return out
-        if out is not None:
-            raise ValueError("out is for io_device environments; a host environment returns a new array")
-        A = 1
-        if actions is not None:
-            if not isinstance(actions, np.ndarray) or actions.dtype != np.int32:
-                raise ValueError("actions must be a numpy int32 array")
-            if actions.ndim == 1:
-                actions = actions.reshape(-1, 1)
-            if actions.ndim != 2 or actions.shape[0] != B:
-                raise ValueError(f"actions must have shape ({B}, A) or ({B},)")
-            A = int(actions.shape[1])
-            actions = np.ascontiguousarray(actions)
-        check_A(A)
-        res = np.zeros((B, A, R, ncol), np.float64)
-        self._check(self.lib.ongym_playout(self._h, A, actions.ctypes.data if actions is not None else None, H, policy, R,
-                                           C.c_uint64(seed), flags, res.ctypes.data), "ongym_playout")
-        return res
+        io = io_for(self)
+        actions, A = self._actions(io, actions, samples=R)
+        (res,), ret = io.outputs(out, [("out", np.float64, (B, A, R, ncol))], f"a float64 tensor of shape (B, A, R, {ncol})",
+                                 detail=False)
+        io.call("ongym_playout", A, io.ptr(actions), H, policy, R, C.c_uint64(seed), flags, io.ptr(res))
+        return ret
 
     # ---- queries (plugin API) ----------------------------------------------------------------------------------------
     def available_slots(self, replica: int, path_id: int) -> np.ndarray:
