@@ -667,6 +667,15 @@ __device__ __forceinline__ void gn_to_db(const GnLin &g, double out[3]) {   // c
 // the band around the limit in which the reference's dB expression decides; every text of the rule outside k_fast is written on it.
 constexpr double kQotBand = 1e-9;
 
+// ---- the tie rule of the scored policies' winner: heuristic_highest_snr replaces its best candidate on a strict `osnr >
+// best_osnr` (heuristics.py:316), and two equal routes are exact ties there, which the first one wins.  The device sums a route's
+// terms in another order, so a later candidate takes the lead only when it is better by more than kTieBandDb.  The band is sized
+// from the exempt zone of DESIGN section 2 ("Decision exactness"): a tenth of its 1e-11 dB, and 140 times the largest difference
+// e = 7.1e-15 dB measured between a device GSNR and the oracle's (tests/test_gpu_tie_ladder.py asserts 4 e below the band).
+// kTieBandRel is the same number on the linear 1/GSNR, where the lean kernels compare: 10^(-d/10) = 1 - d ln10/10 to first order.
+constexpr double kTieBandDb = 1e-12;
+constexpr double kTieBandRel = kTieBandDb * 0.23025850929940457;       // ln(10) / 10
+
 // 1/GSNR `acc` against lim = 10^(-thr_db/10); inside the band the reference's 10 log10(1/acc) >= thr_db
 // (heuristics.py:957-958, envs/qrmsa.pyx:911), so the decision is the dB-domain one everywhere.  A value per lane.
 __device__ __forceinline__ bool qot_pass(double acc, double lim, double thr_db) {
@@ -2040,9 +2049,8 @@ __device__ __forceinline__ void policy_highest_snr(Ctx &c, int src, int dst, dou
                 }
                 if (__ballot(fail)) any_osnr = 1;
                 const double vmax = wave_max_f64(v);
-                if (vmax > best_osnr + 1e-9) {                            // tie noise in dB, not kQotBand: strict, beyond the rounding noise (exact ties of
-                                                                          // the reference: equal routes on an empty network; see eval_cands in
-                                                                          // ongym_fast.hpp): the first maximum wins
+                if (vmax > best_osnr + kTieBandDb) {                      // strict, beyond the rounding noise (exact ties of the reference: equal
+                                                                          // routes; see eval_cands in ongym_fast.hpp): the first maximum wins
                     const uint64_t bal = __ballot(v == vmax);
                     const int ln = __ffsll((unsigned long long)bal) - 1;
                     best_osnr = vmax;

@@ -1271,6 +1271,8 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                         const double fc = P.f0 + (P.slot_bw * (int)ss[a]) + c_h;           // envs/qrmsa.pyx:901-905
                         gase[a] = (c_bw * fc * pr.ase) * rp0;
                     }
+                    // highest SNR: a candidate whose partial sum has reached best_acc cannot take the lead (the tie rule below asks
+                    // for less than best_acc (1 - kTieBandRel)); the exit keeps to the rule's safe side and drops no possible winner
                     const double thr = POL == ONGYM_POLICY_HIGHEST_SNR ? fmin(c_hi, best_acc) : c_hi;
                     const int x_lo = 2 * (int)xlist[j0] + nn, x_hi = 2 * (int)xlist[min(j0 + NA * kWave, cnt) - 1] + nn;     // span of the pass's centres
                     bool cut = false;
@@ -1341,9 +1343,10 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                             const double v = ok ? acc : INFINITY;
                             const double vmin = wave_min_f64(v);
                             // a new best must beat the old one by more than the rounding noise between this sum and the
-                            // reference's (different association: ~1e-13): candidates whose 1/GSNR agree to 1e-10 are exact ties
-                            // in the reference (equal routes on an empty network) and the first one keeps the lead there
-                            if (vmin < best_acc * (1.0 - 1e-10)) {
+                            // reference's (different association): candidates whose 1/GSNR agree to kTieBandRel (ongym_device.hpp,
+                            // the generic kernel's kTieBandDb on the linear value) are exact ties in the reference (equal routes)
+                            // and the first one keeps the lead there
+                            if (vmin < best_acc * (1.0 - kTieBandRel)) {
                                 const int ln = __builtin_ctzll(__ballot(v == vmin));
                                 best_acc = vmin; ch_acc = vmin;
                                 ch_k = k; ch_m = m; ch_n = nn; ch_path = path; ch_mask = pmask; ch_slot = (int)rl(ss[a], ln);

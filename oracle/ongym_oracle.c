@@ -379,6 +379,10 @@ static void gn_state(orc_env *e, int path_id, int slot, int n, double out[3], in
             count ? &e->total_terms : 0);
 }
 void orc_gn(orc_env *e, int path_id, int slot, int n, double out[3]) { gn_state(e, path_id, slot, n, out, 0); }
+/* orc_gn of `count` candidates (path, slot, nslots) against one state: out[count][3] */
+void orc_gn_many(orc_env *e, const int32_t *cands, int count, double *out) {
+    for (int i = 0; i < count; i++) gn_state(e, cands[3 * i], cands[3 * i + 1], cands[3 * i + 2], &out[3 * i], 0);
+}
 
 /* GN of a RUNNING service against the current state, itself excluded by service_id (core/osnr.pyx:65) */
 static void gn_running(orc_env *e, int32_t si, double out[3]) {

@@ -50,6 +50,8 @@ def lib():
         L.orc_candidates.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int]
         L.orc_is_path_free.argtypes = [vp, C.c_int, C.c_int, C.c_int]
         L.orc_gn.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
+        L.orc_gn_many.argtypes = [vp, vp, C.c_int, vp]
+        L.orc_gn_many.restype = None
         L.orc_gn_lists.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
         L.orc_encode_action.argtypes = [vp, C.c_int, C.c_int, C.c_int]
         L.orc_decode_action.argtypes = [vp, C.c_int, vp]
@@ -126,6 +128,13 @@ class OracleEnv:
     def gn(self, path_id, slot, n) -> np.ndarray:
         out = np.zeros(3)
         self.L.orc_gn(self.h, path_id, slot, n, out.ctypes.data)
+        return out
+
+    def gn_many(self, cands) -> np.ndarray:
+        """gn of every (path_id, slot, n) of `cands` against the current state: float64 [len(cands), 3]."""
+        cands = np.ascontiguousarray(cands, np.int32).reshape(-1, 3)
+        out = np.zeros((len(cands), 3))
+        self.L.orc_gn_many(self.h, cands.ctypes.data, len(cands), out.ctypes.data)
         return out
 
     def gn_lists(self, path_id, slot, n, counts, intf) -> np.ndarray:
