@@ -503,6 +503,46 @@ int ongym_repair_links(ongym_env *env, const uint64_t *sets, int32_t per_replica
  * Read-only.  Refused (ONGYM_E_ARG): NULL failed_out.  Buffers and timing as ongym_cut_links'. */
 int ongym_failed_links(ongym_env *env, uint64_t *failed_out);
 
+/* The spectrum map of every replica: who holds every slot, the running records of all replicas, and an audit of the rule that
+ * every call which changes a replica keeps: the used cells of the bitmap are exactly the disjoint union of the running records'
+ * provisioned ranges (E = n_links in table order, S = n_slots, C = capacity, P = n_paths, M = n_mods).
+ * Records   A = the replica's `active` clamped to [0, C].  Record i < A, in ongym_query_services' order, is decoded from the
+ *           stored words.  It is well-formed iff 0 <= path < P, n >= 1, slot + n <= S, format < M and, under the 32-bit-mask
+ *           record codec (E <= 32, P <= 512), its mask word is the low word of its route's link mask.
+ * Claims    a well-formed record claims, on every link of its route, its signal cells [slot, slot + n) and the guard cell
+ *           slot + n if slot + n < S.  A malformed record claims nothing.
+ * Failed    a link whose row has no free slot in [0, S) and that no well-formed record's route contains (ongym_failed_links).
+ * Width     the widest record ongym_move_services may write on this environment (its "Width" above).
+ * owner_out   int16 [batch][E][S], 2 E S bytes per replica (NSFNET, S = 320, batch 65 536: 0.9 GB): v >= 0 a signal cell of
+ *             record v; -1 free in the bitmap and unclaimed; -32767 <= v <= -2 the guard cell of record -2 - v; -32768 used in
+ *             the bitmap and unclaimed (a failed link's cells, or an orphan).  A cell with several claimants shows the claim of
+ *             the lowest record index; a claimed cell shows its claim whatever the bitmap says.  Needs C <= 32766
+ *             (ONGYM_E_LIMIT otherwise; the other three outputs take any capacity).
+ * rec_out     int32 [batch][C][6]: path_id, slot, nslots, modulation, service_id (-1 unless ids are kept), flags (bit 0: in
+ *             the disrupted list, the sign of the stored release time; bit 1: malformed).  Rows at and beyond A: all -1.
+ * release_out float32 [batch][C]: the release time without its sign; NaN at and beyond A.  For well-formed records rec_out and
+ *             release_out equal ongym_query_services field for field.
+ * audit_out   int32 [batch][10]:
+ *             0 violations          bit 0: `active` outside [0, C]; bits 1-5: columns 2, 3, 4, 5, 6 non-zero
+ *             1 records             A
+ *             2 malformed           records that are not well-formed
+ *             3 overlap_cells       cells with two or more claimants
+ *             4 claimed_free_cells  cells with a claimant whose bitmap bit says free
+ *             5 orphan_cells        used, unclaimed cells on links that are not failed
+ *             6 over_width          well-formed records with n above the width limit
+ *             7 failed_links        their count (information)
+ *             8 claimed_cells       cells with at least one claimant (information)
+ *             9 used_cells          used bits in [0, S) over all links (information)
+ *             With violations = 0, column 9 = column 8 + S x column 7.
+ * Not audited, deliberately: release times, service ids (quirk Q12 allows duplicates), statistics and the pending request.
+ * Defined on any state ongym_state_load accepts: no record field and no `active` is used as an index before its range check.
+ * Any pointer may be NULL, not all four (ONGYM_E_ARG).  Read-only: no replica state, statistic, counter, disrupted flag, move
+ * log or stream position changes.  ONGYM_E_LIMIT: the LDS block (24 bytes per row word; with owner_out 4 S + 8 C more)
+ * exceeds 160 KiB.  Buffers: host buffers (staged through a device buffer grown on demand; the call synchronises once), or
+ * device buffers with cfg.io_device (then the call only launches on the environment's stream and nothing synchronises).
+ * ongym_last_kernel_ms times the kernel. */
+int ongym_spectrum_map(ongym_env *env, int16_t *owner_out, int32_t *rec_out, float *release_out, int32_t *audit_out);
+
 /* Moves running lightpaths on LIVE replicas: a chosen record is placed again, at a chosen action or where first fit puts it
  * (K = k_paths, M = n_mods, S = n_slots, C = capacity, N = n_moves).  A move is a restoration of ongym_cut_links with one victim
  * and no failed link, written back to the victim's own record index.

@@ -30,6 +30,7 @@
 #include "ongym_impact.hpp"        // effect of candidate actions on the running lightpaths (ongym_action_impact)
 #include "ongym_failure.hpp"       // link failures and first-fit restoration (ongym_failure_impact, ongym_failure_sets)
 #include "ongym_cut.hpp"           // link failures on live replicas (ongym_cut_links, ongym_repair_links, ongym_failed_links)
+#include "ongym_spectrum.hpp"      // slot owners, batched records and the state audit (ongym_spectrum_map)
 #include "ongym_move.hpp"          // running lightpaths moved on live replicas (ongym_move_services)
 #include "ongym_admission.hpp"     // first-fit admission of every node pair and bit rate (ongym_admission_map)
 #include "ongym_playout.hpp"       // candidate actions followed by H policy steps on a private copy (ongym_playout)
@@ -1544,6 +1545,39 @@ int ongym_failed_links(ongym_env *env, uint64_t *failed_out) {
     return rc ? rc : stage_close(env, sp);
 }
 
+// The widest record a lean step kernel of this environment can carry: where one may run, it carries no slot count above its pair
+// table's rows and, in the narrow build, above 32 (ongym_fast.hpp, "Eligibility"); otherwise any width up to S
+static int lean_width_limit(const ongym_env *env) {
+    const Params &P = env->P;
+    const int max_slots = (env->fast_ok && !env->trace_used) ? std::min(P.tab_nmax, env->fast_wide ? 512 : 32) : P.n_slots;
+    return std::min(max_slots, P.n_slots);
+}
+
+int ongym_spectrum_map(ongym_env *env, int16_t *owner_out, int32_t *rec_out, float *release_out, int32_t *audit_out) {
+    if (!env) return ONGYM_E_ARG;
+    if (!owner_out && !rec_out && !release_out && !audit_out)
+        return fail_arg(env, "null owner_out/rec_out/release_out/audit_out: nothing to compute");
+    const Params &P = env->P;
+    if (owner_out && P.capacity > kSpectrumMaxOwners)
+        return fail_arg(env, "owner_out holds record indices in an int16: it needs capacity <= 32766", ONGYM_E_LIMIT);
+    const size_t lds = spectrum_lds_bytes(P, owner_out != nullptr);
+    if (lds > 160 * 1024) return fail_arg(env, "the spectrum kernel's LDS block exceeds 160 KiB: lower capacity", ONGYM_E_LIMIT);
+    HIP_TRY(env, hipSetDevice(env->cfg.device));
+    const size_t B = (size_t)P.batch, C = (size_t)P.capacity;
+    Span sp[] = {{owner_out, B * P.n_links * P.n_slots * sizeof(int16_t), kOut},                   // staging: owner_out | rec_out | release_out | audit_out
+                 {rec_out, B * C * kSpectrumRec * sizeof(int32_t), kOut}, {release_out, B * C * sizeof(float), kOut},
+                 {audit_out, B * kSpectrumAudit * sizeof(int32_t), kOut}};
+    int rc;
+    if ((rc = stage_open(env, env->stage[kStageSpectrum], sp))) return rc;
+    rc = timed_launch(env, [&] {
+        return with_layout(P, [&](auto, auto R32) {     // the stored record codec
+            return launch_lds(env, k_spectrum_map<R32>, dim3(P.batch), lds, env->d_P, lean_width_limit(env), sp[0].as<int16_t>(),
+                              sp[1].as<int32_t>(), sp[2].as<float>(), sp[3].as<int32_t>());
+        });
+    });
+    return rc ? rc : stage_close(env, sp);
+}
+
 int ongym_move_services(ongym_env *env, int32_t n_moves, const int32_t *moves, int32_t flags, double *move_out) {
     if (!env) return ONGYM_E_ARG;
     if (!moves || !move_out) return fail_arg(env, "null moves/move_out");
@@ -1551,9 +1585,6 @@ int ongym_move_services(ongym_env *env, int32_t n_moves, const int32_t *moves, i
     if (flags & ~ONGYM_MOVE_OWN_ROUTE) return fail_arg(env, "unknown flags: only ONGYM_MOVE_OWN_ROUTE is defined");
     if (int rc = cut_refusals(env)) return rc;
     const Params &P = env->P;
-    // the widest record a move may write: a lean step kernel may run on this environment later, and it carries no slot count
-    // above its pair table's rows and, in the narrow build, above 32 (ongym_fast.hpp, "Eligibility")
-    const int max_slots = (env->fast_ok && !env->trace_used) ? std::min(P.tab_nmax, env->fast_wide ? 512 : 32) : P.n_slots;
     const size_t lds = move_lds_bytes(P);
     if (lds > 160 * 1024) return fail_arg(env, "the move kernel's LDS block exceeds 160 KiB: lower capacity", ONGYM_E_LIMIT);
     HIP_TRY(env, hipSetDevice(env->cfg.device));
@@ -1564,7 +1595,7 @@ int ongym_move_services(ongym_env *env, int32_t n_moves, const int32_t *moves, i
     rc = timed_launch(env, [&] {
         return with_layout(P, [&](auto UA, auto R32) {     // attenuation and the stored record codec
             return launch_lds(env, k_move_services<UA, R32>, dim3(P.batch), lds, env->d_P, (int)n_moves,
-                              sp[1].as<const int32_t>(), (int)((flags & ONGYM_MOVE_OWN_ROUTE) != 0), std::min(max_slots, P.n_slots),
+                              sp[1].as<const int32_t>(), (int)((flags & ONGYM_MOVE_OWN_ROUTE) != 0), lean_width_limit(env),
                               env->d_path_pair,
                               sp[0].as<double>());
         });

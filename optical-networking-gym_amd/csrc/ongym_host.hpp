@@ -26,6 +26,7 @@ enum {
     kStageReset,    // ongym_reset, _reset_episode_counters: the mask; these two return without synchronising
     kStageQuery,    // the ongym_query_* calls: used with io_device too (query results are always host buffers)
     kStageMove,     // ongym_move_services: move_out | moves
+    kStageSpectrum, // ongym_spectrum_map: owner_out | rec_out | release_out | audit_out
     kStages
 };
 

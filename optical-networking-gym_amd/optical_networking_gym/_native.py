@@ -46,6 +46,12 @@ CUT_LINKS = FAILURE_SETS + ("dropped",)                               # ongym_cu
 CUT_NO_RESTORE = 1                                                    # ... its flag: every victim is dropped, none restored
 MOVE_TOP, MOVE_FIRST_FIT, MOVE_OWN_ROUTE = -1, -1, 1                   # ongym_move_services: record selector, target selector, flag
 MOVE_COLUMNS = ("status", "record", "old_action", "new_action", "margin", "slot_hops_delta")   # ... move_out entries per (replica, move)
+SPECTRUM_AUDIT_COLUMNS = ("violations", "records", "malformed", "overlap_cells", "claimed_free_cells", "orphan_cells", "over_width",
+                          "failed_links", "claimed_cells", "used_cells")   # ongym_spectrum_map: audit_out entries per replica
+SPECTRUM_RECORD_COLUMNS = ("path_id", "slot", "nslots", "modulation", "service_id", "flags")   # ... rec_out entries per record
+SPECTRUM_DISRUPTED, SPECTRUM_MALFORMED = 1, 2                # ... the bits of its flags column
+OWNER_FREE, OWNER_GUARD_BASE, OWNER_UNOWNED = -1, -2, -32768  # ... owner_out: free; guard cell of record i = -2 - i; used, unclaimed
+MAX_OWNER_CAPACITY = 32766                                  # ... owner_out needs capacity <= this
 ADMISSION_MAP = ("status", "admitted", "blocked_no_spectrum", "blocked_qot", "blocking_probability", "bit_rate_blocking",
                  "lowest_margin", "detoured")                # ongym_admission_map: summary_out entries per (replica, action)
 MAX_ADMISSION_RATES = 16                                    # ... and the longest rate list
@@ -260,6 +266,9 @@ def _declare(lib):
     if hasattr(lib, "ongym_move_services"):     # (an older build named by ONGYM_HIP_LIB has none)
         lib.ongym_move_services.argtypes = [vp, C.c_int32, vp, C.c_int32, vp]
         lib.ongym_move_services.restype = C.c_int32
+    if hasattr(lib, "ongym_spectrum_map"):      # (an older build named by ONGYM_HIP_LIB has none)
+        lib.ongym_spectrum_map.argtypes = [vp, vp, vp, vp, vp]
+        lib.ongym_spectrum_map.restype = C.c_int32
     if hasattr(lib, "ongym_admission_map"):     # (an older build named by ONGYM_HIP_LIB has none)
         lib.ongym_admission_map.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp]
         lib.ongym_admission_map.restype = C.c_int32
@@ -334,7 +343,7 @@ def _declare_tail(lib, vp, skip=()):
 
 EXPORTED_SYMBOLS = (
     "ongym_create", "ongym_destroy", "ongym_seed", "ongym_seed_base", "ongym_set_requests", "ongym_reset", "ongym_reset_episode_counters", "ongym_step_policy",
-    "ongym_step_actions", "ongym_step_actions_bundle", "ongym_policy_actions", "ongym_observe", "ongym_observe_blocks", "ongym_link_metrics", "ongym_service_qot", "ongym_action_impact", "ongym_failure_impact", "ongym_failure_sets", "ongym_cut_links", "ongym_repair_links", "ongym_failed_links", "ongym_move_services", "ongym_admission_map", "ongym_playout", "ongym_sample_actions", "ongym_masked_categorical", "ongym_masked_categorical_backward",
+    "ongym_step_actions", "ongym_step_actions_bundle", "ongym_policy_actions", "ongym_observe", "ongym_observe_blocks", "ongym_link_metrics", "ongym_service_qot", "ongym_action_impact", "ongym_failure_impact", "ongym_failure_sets", "ongym_cut_links", "ongym_repair_links", "ongym_failed_links", "ongym_move_services", "ongym_spectrum_map", "ongym_admission_map", "ongym_playout", "ongym_sample_actions", "ongym_masked_categorical", "ongym_masked_categorical_backward",
     "ongym_masked_categorical_rows", "ongym_masked_categorical_backward_rows", "ongym_gae", "ongym_state_size", "ongym_state_save", "ongym_state_load", "ongym_fork", "ongym_query_available", "ongym_query_gsnr", "ongym_query_gsnr_many", "ongym_query_moves", "ongym_query_grid",
     "ongym_query_services", "ongym_query_request", "ongym_query_candidates", "ongym_query_path_free",
     "ongym_stats_get", "ongym_sync", "ongym_set_stream", "ongym_last_kernel_ms", "ongym_query_occupancy", "ongym_query_occupancy_policy",

@@ -478,6 +478,75 @@ class BatchedQRMSAEnv:
         moves = np.tile(np.array([nat.MOVE_TOP, nat.MOVE_FIRST_FIT], np.int32), (int(n), 1))
         return self.move_services(moves, own_route=own_route)
 
+    # ---- slot owners, batched records and the state audit (ongym_spectrum_map, include/ongym.h) -----------------------------
+    def spectrum_map(self, out=None, owners=True, records=False, audit=True):
+        """Who holds every slot, the running records of all replicas and an audit of the state, for every replica in one call:
+        a dict of the arrays asked for.  owners: int16 [B, E, S] (2 E S bytes per replica), v >= 0 a signal cell of record v,
+        nat.OWNER_FREE free, -2 - v the guard cell of record v, nat.OWNER_UNOWNED used and unclaimed (a failed link, or an
+        orphan); decode_owners splits it.  records (with release): int32 [B, C, 6], columns nat.SPECTRUM_RECORD_COLUMNS, and
+        float32 [B, C]; rows at and beyond the running count are -1 and NaN; record i is services(r)[i].  audit: int32 [B, 10],
+        columns nat.SPECTRUM_AUDIT_COLUMNS: column 0 is zero exactly when the bitmap is the disjoint union of the records'
+        provisioned ranges, every record is well-formed and none is wider than move_services may write.  The library refuses
+        owners for a capacity above nat.MAX_OWNER_CAPACITY (the other outputs take any capacity).  Read-only.  A host
+        environment returns numpy arrays.  An io_device environment writes into `out`, a dict of torch tensors on its device
+        with exactly the keys asked for, on torch's current stream (env.set_stream), without synchronising."""
+        c = self.holder.struct
+        B, Cp = self.batch_size, c.capacity
+        want = [("owners", np.int16, (B, c.n_links, c.n_slots))] if owners else []
+        want += [("records", np.int32, (B, Cp, len(nat.SPECTRUM_RECORD_COLUMNS))), ("release", np.float32, (B, Cp))] if records else []
+        want += [("audit", np.int32, (B, len(nat.SPECTRUM_AUDIT_COLUMNS)))] if audit else []
+        if not want:
+            raise ValueError("nothing to compute: ask for owners, records or audit")
+        names = [w[0] for w in want]
+        io = io_for(self)
+        if out is not None and c.io_device:
+            if not isinstance(out, dict) or sorted(out) != sorted(names):
+                raise ValueError(f"out must be a dict with exactly the keys {names}")
+            out = tuple(out[n] for n in names)
+        arrays, _ = io.outputs(out, want)
+        got = dict(zip(names, arrays))
+        io.call("ongym_spectrum_map", *(io.ptr(got.get(n)) for n in ("owners", "records", "release", "audit")))
+        return got
+
+    @staticmethod
+    def decode_owners(owners):
+        """(record, kind) of an owners array of spectrum_map, both of its shape (numpy int32, or torch.int32 on its device):
+        kind 0 free, 1 signal, 2 guard, 3 used and unclaimed; record is the holder's index, -1 where there is none."""
+        if isinstance(owners, np.ndarray):
+            if owners.dtype != np.int16:
+                raise ValueError("owners must be an int16 array")
+            o, where, xp = owners.astype(np.int32), np.where, np
+        else:
+            import torch
+            if not isinstance(owners, torch.Tensor) or owners.dtype != torch.int16:
+                raise ValueError("owners must be an int16 array or tensor")
+            o, where, xp = owners.to(torch.int32), torch.where, torch
+        kind = where(o >= 0, xp.ones_like(o), where(o == nat.OWNER_FREE, xp.zeros_like(o),
+                                                    where(o == nat.OWNER_UNOWNED, xp.full_like(o, 3), xp.full_like(o, 2))))
+        record = where(kind == 1, o, where(kind == 2, nat.OWNER_GUARD_BASE - o, xp.full_like(o, -1)))
+        return record, kind
+
+    def check_state(self):
+        """The audit of spectrum_map alone, int32 [B, 10] as a numpy array (an io_device environment runs it on torch's
+        current stream and copies it back): raises OngymError naming the first replica with a violation and its non-zero
+        columns, returns the audit otherwise."""
+        if self.holder.struct.io_device:
+            import torch
+            from .. import rl
+            t = torch.empty((self.batch_size, len(nat.SPECTRUM_AUDIT_COLUMNS)), dtype=torch.int32, device=rl._device(self))
+            audit = self.spectrum_map(out={"audit": t}, owners=False)["audit"].cpu().numpy()
+        else:
+            audit = self.spectrum_map(owners=False)["audit"]
+        bad = np.flatnonzero(audit[:, 0])
+        if bad.size:
+            r = int(bad[0])
+            cols = ", ".join(f"{n} = {int(v)}" for n, v in zip(nat.SPECTRUM_AUDIT_COLUMNS[2:7], audit[r, 2:7]) if v)
+            if audit[r, 0] & 1:
+                cols = "active outside [0, capacity]" + (", " + cols if cols else "")
+            raise OngymError(f"check_state: {bad.size} of {self.batch_size} replicas violate the state invariants; the first is "
+                             f"replica {r}: {cols}")
+        return audit
+
     # ---- first-fit admission of every node pair and bit rate (ongym_admission_map, include/ongym.h) ------------------------
     @property
     def admission_pairs(self) -> np.ndarray:

@@ -492,6 +492,18 @@ class QRMSAEnv:
         route = self.k_shortest_paths[self.current_service.source, self.current_service.destination][path]
         return [grid[self.topology[l.node1][l.node2]["index"], :] for l in route.links]
 
+    @property
+    def spectrum_slots_allocation(self) -> np.ndarray:
+        """int64 [E, S]: the service_id that holds each slot of each link (links by their "index"), -1 where none does, as the
+        reference keeps it (qrmsa.pyx:486, 1303): a service's id over its slots and its guard slot.  From the device's owner
+        map and records (BatchedQRMSAEnv.spectrum_map); needs an environment that keeps service ids."""
+        if not self._tracks_ids:
+            raise ValueError("spectrum_slots_allocation needs service ids: create the environment with track_service_ids=True")
+        m = self._dev.spectrum_map(owners=True, records=True, audit=False)
+        record, _ = BatchedQRMSAEnv.decode_owners(m["owners"][0])
+        ids = np.append(m["records"][0][:, 4].astype(np.int64), -1)      # record -1 (no holder) reads the appended -1
+        return ids[record]
+
     def _get_network_compactness(self) -> float:
         """Spectrum compactness of the whole network, qrmsa.pyx:1150-1186: (occupied span summed over links / slot-hops of the
         running services) x (links / free blocks inside the occupied spans); 1.0 when no link has a free block inside its

@@ -47,6 +47,7 @@ for topo, S, pid, B, steps in CASES:
     while done < steps:
         n = min(500, steps - done)
         env.step_policy(n, record=False, policy=pid); done += n
+        env.check_state()                     # every replica after every chunk: raises on the first violated invariant
     st = env.stats()
     t0 = time.time()
     oracles = []
