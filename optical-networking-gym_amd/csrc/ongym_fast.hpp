@@ -349,6 +349,14 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
 #endif
     static_assert(!(LWT && M64), "the weight table needs link masks of one word");
     constexpr bool kLwt = LWT;
+    // Branch layout ("Branches on a request's path"): FF_COLD(c) tells the compiler that `c` is rarely true, so
+    // the block behind it is laid out behind the step loop's hot code and a request's common path falls through the test instead
+    // of jumping over the block; FF_HOT(c) the reverse.  First fit only: the other policies' kernels keep their code byte for byte
+    // (the constant condition leaves no trace of the hint in them).
+    // (the condition of kFrRoute0 / kFrInPlace below, which are defined from it: pop_request needs it before them)
+    constexpr bool kFfHints = POL == ONGYM_POLICY_FIRST_FIT && !REC;
+#define FF_COLD(c) (kFfHints ? (bool)__builtin_expect(!!(c), 0) : (bool)(c))
+#define FF_HOT(c) (kFfHints ? (bool)__builtin_expect(!!(c), 1) : (bool)(c))
     const int lane = threadIdx.x, replica = blockIdx.x;
     const int E = P.n_links, RW = P.row_words * 2, C = P.capacity, S = P.n_slots, M = P.n_mods, K = P.k_paths, N = P.n_nodes;
     DevEnv *const ge = P.env + replica;
@@ -581,8 +589,8 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
 
     // next request: pop the ring, advance the float32 clock (envs/qrmsa.pyx:1079-1111)
     auto pop_request = [&]() {
-        if (rq_pos == kWave) { req_base += kWave; refill(); }
-        if (TRACE && (long long)(req_base + (uint64_t)rq_pos) >= P.trace_n) {      // trace exhausted (see draw_next)
+        if (FF_COLD(rq_pos == kWave)) { req_base += kWave; refill(); }
+        if (TRACE && FF_COLD((long long)(req_base + (uint64_t)rq_pos) >= P.trace_n)) {      // trace exhausted (see draw_next)
             have = false; d_flags |= ONGYM_F_NO_REQUEST;
             return;
         }
@@ -601,7 +609,7 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
     // pair loop without a test, and with one mask word a departure tests its link against the lane's own bit (kFrLaneBit).  The
     // kernels that write records keep the plain forms: with these their 5-wave instantiations spill more vector registers.  The
     // other policies keep them too, and with them the parent's registers.
-    constexpr bool kFrRoute0 = POL == ONGYM_POLICY_FIRST_FIT && !REC, kFrInPlace = kFrRoute0;
+    constexpr bool kFrRoute0 = kFfHints, kFrInPlace = kFrRoute0;
     constexpr bool kFrPathAnd = kFrRoute0, kFrLaneBit = kFrRoute0 && !M64;
     uint32_t lane_bit = lane < 32 ? 1u << lane : 0u;        // defined once per launch; pinned, or the shift comes back at every use
     if (kFrLaneBit) asm volatile("" : "+v"(lane_bit));
@@ -617,7 +625,9 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
     auto path_and = [&](uint64_t links64, uint32_t rows = kPathRowsLong) -> uint32_t {
         const int wl = kFrRows && RW <= kPathRowsLanes ? min(lane & (kPathRowsLanes - 1), RW - 1) : min(lane, RW - 1);
         uint32_t x = lane < RW ? ~0u : 0u;
-        if (kFrRows && (int32_t)rows >= 0) {
+        // (one way out for both forms: with an early return behind the four-hop form the join was an `s_cbranch_execnz` that is
+        //  always taken, with an `s_branch` behind it)
+        if (kFrRows && FF_HOT((int32_t)rows >= 0)) {
             const uint32_t l = __builtin_amdgcn_ubfe(rows, (uint32_t)(lane >> 4) * kPathRowsBits + kPathRowsShift, 5u);
             uint32_t y = *(const __attribute__((address_space(3))) uint32_t *)(uintptr_t)
                              (__umul24(l, vz + (uint32_t)RW * 4u) + occ_base + (uint32_t)wl * 4u);
@@ -625,9 +635,7 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
             y = h[0] & h[1];
             const auto f = __builtin_amdgcn_permlane32_swap(y, y, false, false);    // halves lo hi -> lo lo | hi hi
             x &= f[0] & f[1];
-            if (lane == (S >> 5)) x |= 1u << (S & 31);
-            return x;
-        }
+        } else {
         // Two links per trip while two remain: both rows are read before either is used, so a pair costs one LDS round trip
         // (the same instructions per link; no neutral read pads an odd count).  kFrPathAnd: every caller passes the mask of a real
         // route (hops >= 1), so the loop is entered without testing `links` first.
@@ -663,6 +671,7 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                     x &= r0;
                 } while (links);
         }
+        }       // (the link loop)
         if (lane == (S >> 5)) x |= 1u << (S & 31);
         return x;
     };
@@ -819,7 +828,7 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
     }
     FSTAMP(11);
     for (it = 0; it < nsteps; ++it) {
-        if (TRACE && !have) {           // no request source left: the step is a no-op (as in k_run)
+        if (TRACE && FF_COLD(!have)) {           // no request source left: the step is a no-op (as in k_run)
             if (REC && lane == 0) {
                 ongym_step_rec r;
                 memset(&r, 0, sizeof(r));
@@ -926,16 +935,21 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
             if (TRACE) d_acc++;                                                                                                 \
             cnt += (lane == 8 + (c_m) || lane == 24 + cur_bi) ? 1 : 0;                                                          \
             osnr_prod *= (c_acc);                                                                                               \
-            if (osnr_prod < 1e-250) { if (lane == 0) cold[4] += -10.0 * log10(osnr_prod); osnr_prod = 1.0; wave_sync(); }       \
+            if (FF_COLD(osnr_prod < 1e-250)) { if (lane == 0) cold[4] += -10.0 * log10(osnr_prod); osnr_prod = 1.0; wave_sync(); }       \
         }
         bool chosen = false;                // kFrInPlace: a route served the request (or would have: the table is full)
 
         // First fit without records (kFrRoute0) walks the routes from the id that came with the request: 96 % of the accepted
         // requests are served by that first route, so the loop is entered with it (a pair without a route, cur_p0 < 0, tries
         // nothing) and the next route's id is fetched only behind a route that failed.
+        // One exit (kFrRoute0), the test of the loop variable at the bottom, as the format loop has: a route that serves the request
+        // ends the walk by setting the variable to kFrServed behind an asm the compiler cannot thread into a second exit, the last
+        // route that failed by the -1 behind it.  No `break`, no exit code, and `chosen` is read off the variable after the loop.
+        constexpr int kFrServed = -2;
         int fr_path = cur_p0;
         for (int r = 0; kFrRoute0 ? fr_path >= 0 : r < nk;
-             kFrRoute0 ? (void)(fr_path = ++r < K ? uniform_i32(KC(P.pair_paths)[pair_base() + r]) : -1) : (void)r++) {
+             kFrRoute0 ? (void)(fr_path = FF_HOT(fr_path < 0) ? fr_path : ++r < K ? uniform_i32(KC(P.pair_paths)[pair_base() + r]) : -1)
+                       : (void)r++) {
             int k = r, path;
             PathRec pr;
             if (kFrRoute0) {
@@ -1032,7 +1046,9 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
             // the gathers of the evaluation at centre c2 that follows the build (not HIGHEST_SNR, which evaluates by candidates).
             auto build_cache = [&](uint32_t mask_lo, uint32_t mask_hi, uint32_t c2, TabPair (&t)[ENT]) {
                 L = 0;
-                if (FOUR_LIST && four_chunks()) {
+                // (hinted for tables of 256 records and more, where the straight form is the rule.  A smaller table has four_max = -1 and
+                //  always takes the loop form, which this hint lays out as the cold side; that shape was not timed)
+                if (FOUR_LIST && FF_HOT(four_chunks())) {
                     // All four chunks of 64 records in one LDS round trip and no loop (unused entries: mask 0): four tests and
                     // ballots, list positions from v_mbcnt on top of the running count, four EXEC-masked stores.
                     uint2 ab[4];
@@ -1161,6 +1177,7 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
     #pragma unroll              // (a group without interferers has zero weights and zero table values: no select needed)
                 for (int e = 0; e < ENT; e++) part = fma(t[e].x, e_w1[e], fma(-t[e].y, e_pw2[e], part));
                 int x_terms = 0;        // interferer-link terms beyond the register cache
+                if (!kFfHints || __builtin_expect(L > kWave * ENT, 0))      // (a guard in front of the loop, first fit only)
                 for (int base = kWave * ENT; base < L; base += kWave) {       // interferers beyond the register cache
                     const int j = base + lane;
                     if (j < L) {
@@ -1189,7 +1206,7 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                         // inside the 1e-9 band: the reference's own dB-domain expression (see qot_ok)
                         const uint64_t band = grp & ~(yes | __ballot(acc >= l_hi));
                         uint64_t pass = grp & yes;
-                        if (band) pass |= band & __ballot(10.0 * log10(1.0 / acc) >= P.mod_thr[lane & 7] + *KC(&ge->margin));
+                        if (FF_COLD(band != 0)) pass |= band & __ballot(10.0 * log10(1.0 / acc) >= P.mod_thr[lane & 7] + *KC(&ge->margin));
                         ln = pass ? 63 - __builtin_clzll(pass) : -1;                  // the highest format first
                         walked = __popcll(pass ? grp >> ln : grp);
                         if (!pass) rest &= ~(uint32_t)(grp >> (8 * cur_bi));
@@ -1208,14 +1225,17 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                 // highest passing lane is taken whichever of the two tests let it pass, as the walk would.
                 uint64_t pass = __ballot(acc <= l_lo) & grp;
                 const uint64_t open = __ballot(acc < l_hi) & grp, band = open & ~pass;
-                if (band) pass |= band & __ballot(10.0 * log10(1.0 / acc) >= P.mod_thr[lane & 7] + *KC(&ge->margin));
-                int ln = -1, walked;
+                if (FF_COLD(band != 0)) pass |= band & __ballot(10.0 * log10(1.0 / acc) >= P.mod_thr[lane & 7] + *KC(&ge->margin));
+                // (one arm: `if (pass) ... else walked = ...` joined behind an always-taken `s_cbranch_execnz` + `s_branch`)
+                int ln = -1;
+                uint64_t wgrp = grp;                                              // the formats walked: all of the group, or
                 if (pass) {
                     ln = 63 - __builtin_clzll(pass);                              // the highest format first
-                    walked = __popcll(grp >> ln);
+                    wgrp = grp >> ln;                                             // those down to the one that passes
                     ev_acc = readlane_f64(acc, ln);
                     if (REC) { ev_ase = readlane_f64(g_ase, ln); ev_nli = readlane_f64(g_nli, ln); }
-                } else walked = __popcll(grp);
+                }
+                const int walked = __popcll(wgrp);
                 d_evals += walked;
                 lane_terms = (int)(__umul24((uint32_t)(e_terms + x_terms), (uint32_t)walked) + (uint32_t)lane_terms);     // both factors far below 2^24
                 return ln;
@@ -1376,7 +1396,7 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                 if (kRuns) { grp8 = (nr >> 16) & feas; feas &= ~grp8; }
                 else asm("s_bitset0_b32 %0, %1" : "+s"(feas) : "s"(m));
                 const int nn = POL == ONGYM_POLICY_LOWEST_FRAGMENTATION ? n + 1 : n;      // quirk: the request is sized slots + 1 (:357)
-                if (nn + 1 < r_len) { runs = path_and(pmask); r_len = 1; }     // slot counts normally grow as the modulation index falls
+                if (FF_COLD(nn + 1 < r_len)) { runs = path_and(pmask); r_len = 1; }     // slot counts normally grow as the modulation index falls
                 runs = run_and32<WIDE>(runs, r_len, nn + 1);
                 const uint64_t has = __ballot(runs != 0);
                 FSTAMP(2);
@@ -1386,7 +1406,9 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                 if (POL == ONGYM_POLICY_HIGHEST_SNR && !((__ballot(lb < best_acc) >> q) & 1ull)) continue;   // best_acc may have improved
                 // the first start and the width are known: the build issues this evaluation's gathers before it sums the link weights
                 TabPair tv[ENT];
-                if (L < 0) build_cache(pr.mask_lo, pr.mask_hi, (uint32_t)(2 * first + nn), tv);
+                // (true at a route's first evaluation, which 1.09 routes per request see; false at every later one, which then takes the
+                //  jump.  Timed only together with the route loop's exit, on the benchmark's shape: DESIGN.md section 5)
+                if (FF_HOT(L < 0)) build_cache(pr.mask_lo, pr.mask_hi, (uint32_t)(2 * first + nn), tv);
                 else if (POL != ONGYM_POLICY_HIGHEST_SNR) gather((uint32_t)(2 * first + nn), tv);
                 FSTAMP(4);
                 if (POL == ONGYM_POLICY_HIGHEST_SNR) {
@@ -1405,9 +1427,9 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                         // Accepted where the format passes: the candidate goes from the registers it was found in straight to the
                         // provisioning code, and nothing is carried through the loop exits but `chosen` (no record is written here,
                         // so ch_* are not needed).  The loop still has its one exit at the bottom.
-                        if (active >= C) { d_flags |= ONGYM_F_OVERFLOW; erej++; d_rej++; }    // the table is full: a rejection
+                        if (FF_COLD(active >= C)) { d_flags |= ONGYM_F_OVERFLOW; erej++; d_rej++; }    // the table is full: a rejection
                         else ONGYM_PROVISION(ln & 7, first, n, path, pmask, ev_acc)
-                        chosen = true;
+                        asm volatile("s_mov_b32 %0, %1" : "=s"(fr_path) : "n"(kFrServed));
                     } else {
                         ch_k = k; ch_m = ln & 7; ch_slot = first; ch_n = n; ch_path = path;
                         ch_mask = pmask;
@@ -1440,18 +1462,19 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                 } else { ch_k = -1; lf_qot = true; }
                 break;
             }
-            if (kFrInPlace ? chosen : POL != ONGYM_POLICY_HIGHEST_SNR && ch_k >= 0) break;
+            if (!kFrInPlace && POL != ONGYM_POLICY_HIGHEST_SNR && ch_k >= 0) break;
         }
+        if (kFrInPlace) chosen = fr_path == kFrServed;
 
         // ================= step (envs/qrmsa.pyx:838-1065) ==============================================================
         // (accepted in place: the request is provisioned, or its overflow counted, where the format passed; `chosen` says so, and
         //  ch_k is still -1)
         int accepted = ch_k >= 0;
         int rflags = 0;
-        if (accepted && active >= C) { accepted = 0; rflags |= ONGYM_F_OVERFLOW; d_flags |= ONGYM_F_OVERFLOW; }
+        if (accepted && FF_COLD(active >= C)) { accepted = 0; rflags |= ONGYM_F_OVERFLOW; d_flags |= ONGYM_F_OVERFLOW; }
         if (accepted) {
             ONGYM_PROVISION(ch_m, ch_slot, ch_n, ch_path, ch_mask, ch_acc)
-        } else if (!kFrInPlace || !chosen) {
+        } else if (FF_COLD(!kFrInPlace || !chosen)) {
             erej++; d_rej++;
             if (ch_k < 0 && POL == ONGYM_POLICY_LOWEST_FRAGMENTATION && lf_qot) {
                 rflags |= ONGYM_F_QOT_ERROR | ONGYM_F_BLOCKED_OSNR;
@@ -1532,7 +1555,7 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
 
         // the info dict of the terminal step is computed before the next request is drawn (:996-1060)
         const bool term = (epp + 1 == ep_len);
-        if (term) {
+        if (FF_COLD(term)) {
             if (lane == 0) cold[4] += (osnr_prod != 1.0) ? -10.0 * log10(osnr_prod) : 0.0;      // flush_osnr
             osnr_prod = 1.0;
             wave_sync();
@@ -1650,7 +1673,7 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
         const bool terminated = epp == ep_len;
         if (terminated) d_episodes++;
         if (REC && lane == 0) { recp->active = active; recp->terminated = (uint8_t)terminated; }
-        if (terminated && P.auto_reset) {
+        if (FF_COLD(terminated && P.auto_reset)) {
             // reset (:427-504): empty network, episode counters to zero, draw request #0 of the next episode
             for (int i = lane; i < E * RW; i += kWave) occ[i] = word_mask32(i % RW, 0, S);
             for (int i = lane; i < active; i += kWave) { rec[i] = make_uint2(0u, 0u); rr[i] = INFINITY; }
@@ -1698,6 +1721,8 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
         for (int i = 0; i < ONGYM_NSTAMPS; i++) atomicAdd(&P.dbg[i], stamp_acc[i]);
 #endif
 #undef FSTAMP
+#undef FF_COLD
+#undef FF_HOT
 #undef ONGYM_PROVISION
 }
 

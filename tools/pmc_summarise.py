@@ -68,7 +68,7 @@ def main():
         summ["hbm_bytes_per_env_step"] = (2 * avg["FETCH_SIZE"] + avg["WRITE_SIZE"]) * 1024 / env_steps
     for key, c in (("valu_per_env_step", "SQ_INSTS_VALU"), ("salu_per_env_step", "SQ_INSTS_SALU"),
                    ("lds_per_env_step", "SQ_INSTS_LDS"), ("smem_per_env_step", "SQ_INSTS_SMEM"),
-                   ("vmem_per_env_step", "SQ_INSTS_VMEM_RD")):
+                   ("vmem_per_env_step", "SQ_INSTS_VMEM_RD"), ("branch_per_env_step", "SQ_INSTS_BRANCH")):
         if c in per:
             summ[key] = per[c]
     if "SQ_WAVE_CYCLES" in avg:

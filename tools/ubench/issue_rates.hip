@@ -106,6 +106,45 @@ __global__ __launch_bounds__(64) void k_ldslat(unsigned long long *out, int iter
 }
 #undef FIN
 
+// ---- branches (SQ_INSTS_BRANCH; not part of SQ_INSTS_SALU): REP back-to-back branches per iteration, all forward and all inside
+// one asm statement, SCC set to 0 once per statement (one s_cmp per REP branches).  "+ valu": one independent v_add_u32 behind every
+// branch (four registers in turn), reported per (branch, v_add) pair.  The far form skips 32 dwords (128 bytes, two
+// instruction-cache lines of 64 bytes) per branch.
+#define REP_DIV4 16
+#define BR_STR_(x) #x
+#define BR_STR(x) BR_STR_(x)
+static_assert(REP_DIV4 * 4 == REP, "the branch kernels repeat four branches REP / 4 times");
+#define BR4(one) one one one one
+#define BR_NT "s_cbranch_scc1 9f\n"
+#define BR_TK "s_cbranch_scc0 1f\n s_nop 0\n 1:\n"
+#define BR_UN "s_branch 1f\n s_nop 0\n 1:\n"
+#define BR_FAR "s_cbranch_scc0 1f\n .rept 32\n s_nop 0\n .endr\n 1:\n"
+#define BRANCH_KERNEL(name, one)                                                                                    \
+    __global__ __launch_bounds__(64) void name(unsigned long long *out, int iters) {                                \
+        unsigned a0 = threadIdx.x;                                                                                  \
+        for (int it = 0; it < iters; ++it)                                                                          \
+            asm volatile("s_cmp_lg_u32 0, 0\n .rept " BR_STR(REP_DIV4) "\n" BR4(one) ".endr\n 9:\n" : "+v"(a0) : : "scc"); \
+        out[blockIdx.x * 64 + threadIdx.x] = a0;                                                                    \
+    }
+#define BRANCH_VALU_KERNEL(name, one)                                                                               \
+    __global__ __launch_bounds__(64) void name(unsigned long long *out, int iters) {                                \
+        unsigned a0 = threadIdx.x, a1 = 1, a2 = 2, a3 = 3;                                                          \
+        for (int it = 0; it < iters; ++it)                                                                          \
+            asm volatile("s_cmp_lg_u32 0, 0\n .rept " BR_STR(REP_DIV4) "\n"                                         \
+                         one "v_add_u32 %0, %0, %0\n" one "v_add_u32 %1, %1, %1\n"                                  \
+                         one "v_add_u32 %2, %2, %2\n" one "v_add_u32 %3, %3, %3\n"                                  \
+                         ".endr\n 9:\n" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) : : "scc");                        \
+        out[blockIdx.x * 64 + threadIdx.x] = (unsigned long long)(a0 + a1 + a2 + a3);                               \
+    }
+BRANCH_KERNEL(k_br_nt, BR_NT)
+BRANCH_KERNEL(k_br_tk, BR_TK)
+BRANCH_KERNEL(k_br_un, BR_UN)
+BRANCH_KERNEL(k_br_far, BR_FAR)
+BRANCH_VALU_KERNEL(k_brv_nt, BR_NT)
+BRANCH_VALU_KERNEL(k_brv_tk, BR_TK)
+BRANCH_VALU_KERNEL(k_brv_un, BR_UN)
+BRANCH_VALU_KERNEL(k_brv_far, BR_FAR)
+
 typedef void (*kern_t)(unsigned long long *, int);
 struct Entry { const char *name; kern_t k; int insts_per_iter; };
 
@@ -118,7 +157,11 @@ int main() {
     Entry es[] = {{"v_add_u32 (4 indep)", k_valu32, REP}, {"v_add_u32 (dependent)", k_valu32_dep, REP}, {"v_lshlrev_b64", k_shl64, REP},
                   {"v_fma_f64", k_fma64, REP}, {"v_add_f64", k_add64f, REP}, {"v_mul_lo_u32", k_mullo, REP}, {"v_mov_b32_dpp", k_dppmov, REP},
                   {"v_alignbit_b32", k_alignbit, REP}, {"s_add_u32", k_salu, REP}, {"mixed v_add/s_add", k_mixed, REP},
-                  {"v_readlane_b32", k_readlane, REP}, {"ds_read_b32 x4 + wait", k_ldsread, REP}, {"ds_read_b32 dependent", k_ldslat, REP}};
+                  {"v_readlane_b32", k_readlane, REP}, {"ds_read_b32 x4 + wait", k_ldsread, REP}, {"ds_read_b32 dependent", k_ldslat, REP},
+                  {"s_cbranch_scc1 not taken", k_br_nt, REP}, {"s_cbranch_scc0 taken +1", k_br_tk, REP},
+                  {"s_branch +1", k_br_un, REP}, {"s_cbranch_scc0 taken +32", k_br_far, REP},
+                  {"not taken + valu", k_brv_nt, REP}, {"taken +1 + valu", k_brv_tk, REP},
+                  {"s_branch +1 + valu", k_brv_un, REP}, {"taken +32 + valu", k_brv_far, REP}};
     hipEvent_t e0, e1;
     hipEventCreate(&e0); hipEventCreate(&e1);
     printf("CUs %d; clock reported %d kHz. cycles per wave-instruction PER SIMD at 2.4 GHz (lower = faster); waves/SIMD = blocks per CU / 4\n", cus, prop.clockRate);
