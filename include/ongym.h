@@ -242,7 +242,14 @@ int ongym_seed(ongym_env *env, uint64_t seed);
  * reproducible streams.  ongym_seed(env, seed) == ongym_seed_base(env, seed, 0). */
 int ongym_seed_base(ongym_env *env, uint64_t seed, uint64_t replica_base);
 /* Request source B — trace replay: reqs[r*n_per_replica + i] is the i-th request replica r will draw.
- * Used for parity against captured reference traces (each _next_service call consumes one entry). */
+ * Used for parity against captured reference traces (each _next_service call consumes one entry).
+ * Times: every arrival_time is finite with a clear sign bit (so not -0.0 either), every holding_time is not NaN and has a
+ * clear sign bit; a holding_time of +inf is legal (the service never leaves).  Arrival times need not be monotone: when the
+ * clock steps back nothing leaves.  A service leaves when float32(arrival + holding) <= float32(clock), and the sign bit of
+ * a stored release time is the 'disrupted' flag of measure_disruptions, so the step kernels do not agree on a clock below
+ * zero, and no comparison holds with a NaN.  A host trace (io_device = 0) is checked: an entry outside this contract, or
+ * with an invalid node pair or bit rate, returns ONGYM_E_ARG and leaves the earlier request source installed.  A device
+ * trace (io_device = 1) is not read by the host: the same contract is the caller's to keep. */
 int ongym_set_requests(ongym_env *env, const ongym_request *reqs, int64_t n_per_replica);
 
 /* QRMSAEnv.reset (qrmsa.pyx:427-504) on the replicas with mask[r] != 0 (NULL = all).  The mask is read on the stream (a

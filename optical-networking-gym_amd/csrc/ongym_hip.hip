@@ -1141,13 +1141,21 @@ int ongym_set_requests(ongym_env *env, const ongym_request *reqs, int64_t n_per_
     HIP_TRY(env, hipSetDevice(env->cfg.device));
     HIP_TRY(env, hipStreamSynchronize(env->stream));
     size_t n = (size_t)env->P.batch * (size_t)n_per_replica;
-    // validate node indices on the host when the trace is a host buffer (device traces are the caller's contract)
+    // validate node indices and times on the host when the trace is a host buffer (device traces are the caller's contract).
+    // Nothing of the environment has changed when an entry is refused: the earlier request source stays installed.
     if (!env->cfg.io_device) {
         for (size_t i = 0; i < n; i++) {
             const ongym_request &q = reqs[i];
             if (q.source < 0 || q.source >= env->P.n_nodes || q.destination < 0 || q.destination >= env->P.n_nodes ||
                 q.source == q.destination || !(q.bit_rate > 0))
                 return fail_arg(env, "trace entry with invalid node pair / bit rate");
+            // the sign bit of a stored release time is the 'disrupted' flag and the generic kernels compare fabsf of it, the lean
+            // kernels the value itself: a clock below zero (-0.0 included) is one no two kernels agree on; NaN compares false
+            // everywhere.  A holding time of +inf is legal: the service never leaves.
+            if (!std::isfinite(q.arrival_time) || std::signbit(q.arrival_time))
+                return fail_arg(env, "trace entry with an arrival time that is negative (sign bit set), infinite or NaN");
+            if (std::isnan(q.holding_time) || std::signbit(q.holding_time))
+                return fail_arg(env, "trace entry with a holding time that is negative (sign bit set) or NaN");
         }
         if (env->d_trace) { (void)hipFree(env->d_trace); env->d_trace = nullptr; }
         HIP_TRY(env, hipMalloc(&env->d_trace, n * sizeof(ongym_request)));

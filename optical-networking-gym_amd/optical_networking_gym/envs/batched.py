@@ -119,7 +119,11 @@ class BatchedQRMSAEnv:
         self._check(self.lib.ongym_seed_base(self._h, C.c_uint64(seed), C.c_uint64(replica_base)), "ongym_seed_base")
 
     def set_requests(self, requests: np.ndarray):
-        """Trace replay: `requests` is a REQUEST_DTYPE array [batch, n] (or [n] for batch 1)."""
+        """Trace replay: `requests` is a REQUEST_DTYPE array [batch, n] (or [n] for batch 1).  Every arrival_time must be finite
+        with a clear sign bit (-0.0 is refused too), every holding_time not NaN with a clear sign bit (+inf is legal: the
+        service never leaves); arrival times need not be monotone.  The library checks a host trace and raises OngymError on
+        an entry outside this contract, with the earlier request source still installed.  A trace the library reads from device
+        memory (ongym_set_requests of an io_device environment) is not checked: there the same contract is the caller's."""
         req = np.ascontiguousarray(requests, nat.REQUEST_DTYPE)
         if req.ndim == 1:
             req = req[None, :]

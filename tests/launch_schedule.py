@@ -22,6 +22,7 @@ even, and every (configuration, policy group) is run with both parities.
 """
 from __future__ import annotations
 
+import contextlib
 import copy
 import functools
 import os
@@ -107,21 +108,28 @@ def make_oracles(key):
     return out
 
 
-def make_env(key, generic=False):
-    """The device environment of a configuration, reset.  ONGYM_FORCE_GENERIC is read at create."""
-    from optical_networking_gym.envs.batched import BatchedQRMSAEnv
+@contextlib.contextmanager
+def force_generic(on: bool):
+    """ONGYM_FORCE_GENERIC set to 1 (on) or unset (off) while an environment is created (it is read at create), then put back."""
     old = os.environ.get("ONGYM_FORCE_GENERIC")
-    if generic:
+    if on:
         os.environ["ONGYM_FORCE_GENERIC"] = "1"
     else:
         os.environ.pop("ONGYM_FORCE_GENERIC", None)
     try:
-        env = BatchedQRMSAEnv(tables=tables_of(key), batch_size=B, **config_kw(key))
+        yield
     finally:
         if old is None:
             os.environ.pop("ONGYM_FORCE_GENERIC", None)
         else:
             os.environ["ONGYM_FORCE_GENERIC"] = old
+
+
+def make_env(key, generic=False):
+    """The device environment of a configuration, reset."""
+    from optical_networking_gym.envs.batched import BatchedQRMSAEnv
+    with force_generic(generic):
+        env = BatchedQRMSAEnv(tables=tables_of(key), batch_size=B, **config_kw(key))
     if CONFIGS[key].get("trace"):
         env.set_requests(trace_of(key))
     else:

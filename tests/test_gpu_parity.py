@@ -1093,6 +1093,40 @@ def test_c_abi_rejects_bad_arguments_without_touching_the_device():
         env.step_policy(0)
     moves, total = env.moves(0)                       # defragmentation is off: empty, not an error
     assert total == 0 and len(moves) == 0
+    # trace times no two step kernels agree on (include/ongym.h, ongym_set_requests) are refused with ONGYM_E_ARG, and the
+    # earlier request source stays installed: the next steps are the generator's, as on an environment that saw no such call
+    good = np.zeros((2, 8), nat.REQUEST_DTYPE)
+    good["arrival_time"], good["holding_time"] = np.arange(1.0, 9.0, dtype=np.float32), 50.0
+    good["source"], good["destination"], good["bit_rate"] = 0, 3, 40.0
+    for field, value, what in (("arrival_time", -1.0, "arrival time"), ("arrival_time", -0.0, "arrival time"),
+                               ("arrival_time", np.nan, "arrival time"), ("arrival_time", np.inf, "arrival time"),
+                               ("holding_time", -1.0, "holding time"), ("holding_time", -0.0, "holding time"),
+                               ("holding_time", np.nan, "holding time")):
+        bad = good.copy()
+        bad[field][1, 5] = value
+        with pytest.raises(OngymError, match=rf"\(-1\).*{what}"):
+            env.set_requests(bad)
+    twin = make_env(meta, batch=2)
+    twin.seed(3); twin.reset(); twin.step_policy(50, record=False)
+    assert record_bytes(env.step_policy(30)) == record_bytes(twin.step_policy(30))
+    legal = good.copy()
+    legal["holding_time"][0, 2] = np.inf              # legal: the service never leaves
+    legal["arrival_time"][0, 0] = 0.0
+    env.set_requests(legal); env.reset()
+    rec = env.step_policy(7)
+    assert rec["accepted"].all() and np.isinf(env.services(0)["release_time"]).sum() == 1
+    # and a refused trace leaves an installed TRACE as it is: its rows, its length and every replica's position in it
+    for e in (env, twin):
+        e.set_requests(good); e.reset(); e.step_policy(3, record=False)
+    bad = good.copy()
+    bad["arrival_time"][0, 0] = -1.0                  # the first entry read, and a longer trace: nothing of it is taken
+    with pytest.raises(OngymError, match=r"\(-1\).*arrival time"):
+        env.set_requests(np.concatenate([bad, bad], axis=1))
+    assert record_bytes(env.step_policy(6)) == record_bytes(twin.step_policy(6))      # 4 steps replay, then the trace is out
+    for f in ("flags", "active", "current_time", "episode_services_processed", "episode_services_accepted"):
+        assert np.array_equal(env.stats()[f], twin.stats()[f]), f
+    assert (env.stats()["flags"] & nat.F_NO_REQUEST).all()
+    assert [env.request(r).tobytes() for r in range(2)] == [twin.request(r).tobytes() for r in range(2)]
     # create-time limits
     tb = copy.deepcopy(golden_tables("nsfnet"))
     tb.link_alpha = tb.link_alpha.copy(); tb.link_alpha[3] *= 1.1
