@@ -307,6 +307,7 @@ int ongym_observe(ongym_env *env, float *obs, uint8_t *mask);
  * valid.  Needs path_len_norm and max_bit_rate (not slot_bandwidth == channel_width*1e9: the GN model is the step's); refuses
  * n_mods_consider < n_mods (no format window) with ONGYM_E_ARG.  Buffers: host buffers, or device buffers with cfg.io_device
  * (then the call only launches on the environment's stream and nothing synchronises). */
+enum { ONGYM_MAX_BLOCKS = 16 };   /* J at most */
 int ongym_observe_blocks(ongym_env *env, int32_t blocks, float *obs, uint8_t *mask, int32_t *action_map);
 
 /* Spectrum fragmentation of every link of every replica (utils.pyx:61-107; qrmsa.pyx:1150-1186, 1353-1480), E = n_links in
@@ -330,6 +331,7 @@ int ongym_observe_blocks(ongym_env *env, int32_t blocks, float *obs, uint8_t *ma
  * Any pointer may be NULL, not all three (ONGYM_E_ARG).  Read-only: no replica state, statistic or counter changes.  Buffers:
  * host buffers (staged through a device buffer; the call synchronises), or device buffers with cfg.io_device (then the call
  * only launches on the environment's stream and nothing synchronises). */
+enum { ONGYM_N_LINK_METRICS = 8, ONGYM_N_LINK_STATS = 4 };   /* entries per link of link_out, link_stats */
 int ongym_link_metrics(ongym_env *env, float *link_out, double *compactness, double *link_stats);
 
 /* Current quality of transmission of every running lightpath of every replica (core/osnr.pyx:21-142), C = capacity, E = n_links
@@ -350,6 +352,7 @@ int ongym_link_metrics(ongym_env *env, float *link_out, double *compactness, dou
  * included), disrupted flag or random-number position changes.  Buffers: host buffers (staged through a device buffer grown on
  * demand; the call synchronises), or device buffers with cfg.io_device (then the call only launches on the environment's
  * stream and nothing synchronises).  ongym_last_kernel_ms times the kernel. */
+enum { ONGYM_N_SERVICE_QOT = 4, ONGYM_N_REPLICA_QOT = 6, ONGYM_N_LINK_QOT = 3 };   /* entries per row of svc_out, replica_out, link_out */
 int ongym_service_qot(ongym_env *env, double *svc_out, double *replica_out, float *link_out);
 
 /* What each candidate action would do to the lightpaths that are running, before it is taken (A = n_actions, C = capacity).
@@ -380,6 +383,7 @@ int ongym_service_qot(ongym_env *env, double *svc_out, double *replica_out, floa
  * Buffers: host buffers (staged through a device buffer grown on demand; the call synchronises), or device buffers with
  * cfg.io_device (then the call only launches on the environment's stream and nothing synchronises).  ongym_last_kernel_ms
  * times the kernel. */
+enum { ONGYM_N_ACTION_IMPACT = 8, ONGYM_MAX_IMPACT_ACTIONS = 256 };   /* impact_out entries per row; A at most */
 int ongym_action_impact(ongym_env *env, int32_t n_actions, const int32_t *actions, const double *svc_in, double *impact_out);
 
 /* What happens when a fibre is cut: per replica and per failed link of a list, the running lightpaths that go down with the
@@ -425,6 +429,7 @@ int ongym_action_impact(ongym_env *env, int32_t n_actions, const int32_t *action
  * position changes.  Buffers: host buffers (staged through a device buffer grown on demand; the call synchronises), or device
  * buffers with cfg.io_device (then the call only launches on the environment's stream and nothing synchronises).
  * ongym_last_kernel_ms times the kernel. */
+enum { ONGYM_N_FAILURE_IMPACT = 10 };   /* link_out entries per row */
 int ongym_failure_impact(ongym_env *env, int32_t n_fail, const int32_t *links, double *link_out, int32_t *svc_out);
 
 /* What happens when several links go down at once - two fibres, a node (all its links), a shared-risk link group (the fibres
@@ -456,6 +461,7 @@ int ongym_failure_impact(ongym_env *env, int32_t n_fail, const int32_t *links, d
  * position changes.  Buffers: host buffers (staged through a device buffer grown on demand; the call synchronises), or device
  * buffers with cfg.io_device (then the call only launches on the environment's stream and nothing synchronises; sets must be
  * 8-byte aligned).  ongym_last_kernel_ms times the kernel. */
+enum { ONGYM_N_FAILURE_SETS = 12, ONGYM_MAX_FAILURE_SETS = 65535 };   /* set_out entries per row; F at most */
 int ongym_failure_sets(ongym_env *env, int32_t n_sets, const uint64_t *sets, int32_t per_replica, double *set_out,
                        int32_t *svc_out);
 
@@ -496,6 +502,7 @@ int ongym_failure_sets(ongym_env *env, int32_t n_sets, const uint64_t *sets, int
  * route's node pair; ONGYM_E_LIMIT: the LDS block (the state block + 14 C bytes, 26 C with id tracking) exceeds 160 KiB.
  * Buffers: host buffers (staged; the call synchronises), or device buffers with cfg.io_device (the call only launches on the
  * environment's stream and nothing synchronises; sets must be 8-byte aligned).  ongym_last_kernel_ms times the kernel. */
+enum { ONGYM_N_CUT_LINKS = 13 };   /* cut_out entries per replica */
 enum { ONGYM_CUT_NO_RESTORE = 1 };
 int ongym_cut_links(ongym_env *env, const uint64_t *sets, int32_t per_replica, int32_t flags,
                     double *cut_out, int32_t *svc_out, int32_t *index_out);
@@ -548,6 +555,10 @@ int ongym_failed_links(ongym_env *env, uint64_t *failed_out);
  * exceeds 160 KiB.  Buffers: host buffers (staged through a device buffer grown on demand; the call synchronises once), or
  * device buffers with cfg.io_device (then the call only launches on the environment's stream and nothing synchronises).
  * ongym_last_kernel_ms times the kernel. */
+enum { ONGYM_N_SPECTRUM_AUDIT_COLUMNS = 10, ONGYM_N_SPECTRUM_RECORD_COLUMNS = 6 };   /* entries per row of audit_out, rec_out */
+enum { ONGYM_SPECTRUM_DISRUPTED = 1, ONGYM_SPECTRUM_MALFORMED = 2 };                  /* the bits of rec_out's flags column */
+/* owner_out: free and unclaimed; the guard cell of record i reads ONGYM_OWNER_GUARD_BASE - i; used and unclaimed; C at most */
+enum { ONGYM_OWNER_FREE = -1, ONGYM_OWNER_GUARD_BASE = -2, ONGYM_OWNER_UNOWNED = -32768, ONGYM_MAX_OWNER_CAPACITY = 32766 };
 int ongym_spectrum_map(ongym_env *env, int16_t *owner_out, int32_t *rec_out, float *release_out, int32_t *audit_out);
 
 /* Moves running lightpaths on LIVE replicas: a chosen record is placed again, at a chosen action or where first fit puts it
@@ -594,6 +605,7 @@ int ongym_spectrum_map(ongym_env *env, int16_t *owner_out, int32_t *rec_out, flo
  * disagree on a route's node pair; ONGYM_E_LIMIT: the LDS block (the state block + C / 8 bytes) exceeds 160 KiB.
  * Buffers: host buffers (staged; the call synchronises), or device buffers with cfg.io_device (the call only launches on the
  * environment's stream and nothing synchronises).  ongym_last_kernel_ms times the kernel. */
+enum { ONGYM_N_MOVE_COLUMNS = 6 };   /* move_out entries per row */
 enum { ONGYM_MOVE_TOP = -1 };        /* record selector */
 enum { ONGYM_MOVE_FIRST_FIT = -1 };  /* target selector */
 enum { ONGYM_MOVE_OWN_ROUTE = 1 };   /* flag */
@@ -652,6 +664,8 @@ int ongym_move_services(ongym_env *env, int32_t n_moves, const int32_t *moves, i
  * (a buffer for them is allocated at create; the call itself never allocates).  ONGYM_ADMISSION_GROUPS=<g> in the environment at
  * create forces g wavefronts per scenario: a measurement and test knob, not for production (the split changes the order of the
  * sums of columns 4 and 5, i.e. their last bits, and nothing else). */
+/* summary_out entries per row; A and R at most */
+enum { ONGYM_N_ADMISSION_MAP = 8, ONGYM_MAX_ADMISSION_ACTIONS = 256, ONGYM_MAX_ADMISSION_RATES = 16 };
 int ongym_admission_map(ongym_env *env, int32_t n_actions, const int32_t *actions, int32_t n_rates, const float *rates,
                         const double *weights, double *summary_out, int32_t *map_out, float *margin_out);
 
@@ -693,6 +707,9 @@ int ongym_admission_map(ongym_env *env, int32_t n_actions, const int32_t *action
  * Read-only: no replica state, statistic, work counter, random-number position or disrupted flag changes.  Buffers: host
  * buffers (staged through a device buffer grown on demand; the call synchronises), or device buffers with cfg.io_device (then
  * the call only launches on the environment's stream and nothing synchronises).  ongym_last_kernel_ms times the kernel. */
+/* playout_out entries per row; A, R, A R and H at most */
+enum { ONGYM_N_PLAYOUT = 8, ONGYM_MAX_PLAYOUT_ACTIONS = 256, ONGYM_MAX_PLAYOUT_SAMPLES = 64, ONGYM_MAX_PLAYOUT_SCENARIOS = 4096,
+       ONGYM_MAX_PLAYOUT_HORIZON = 4096 };
 enum { ONGYM_PLAYOUT_OWN_STREAM = 1 };
 int ongym_playout(ongym_env *env, int32_t n_actions, const int32_t *actions, int32_t horizon, int32_t policy,
                   int32_t n_samples, uint64_t seed, int32_t flags, double *playout_out);
@@ -885,7 +902,7 @@ double ongym_last_kernel_ms(ongym_env *env);
 const char *ongym_last_error(ongym_env *env);
 /* sizes the host side needs to allocate buffers / check the build */
 int32_t ongym_abi_version(void);
-int32_t ongym_sizeof(int32_t what); /* 0 config, 1 request, 2 step_rec, 3 service, 4 stats */
+int32_t ongym_sizeof(int32_t what); /* 0 config, 1 request, 2 step_rec, 3 service, 4 stats, 5 move */
 
 #ifdef __cplusplus
 }

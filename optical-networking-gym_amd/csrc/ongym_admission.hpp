@@ -29,9 +29,9 @@
 
 namespace ongym {
 
-constexpr int kAdmissionMap = 8;          // summary_out doubles per (replica, action)
-constexpr int kMaxAdmissionRates = 16;
-constexpr int kMaxAdmissionActions = 256;
+constexpr int kAdmissionMap = ONGYM_N_ADMISSION_MAP;   // summary_out doubles per (replica, action)
+constexpr int kMaxAdmissionRates = ONGYM_MAX_ADMISSION_RATES;
+constexpr int kMaxAdmissionActions = ONGYM_MAX_ADMISSION_ACTIONS;
 constexpr int kAdmissionPart = 10;        // partial sums per (replica, action, group): status, admitted, blocked for spectrum,
                                           // blocked on QoT, sum w, sum w rate (blocked), sum w rate (all), lowest margin, detoured, -
 

@@ -26,7 +26,7 @@
 
 namespace ongym {
 
-constexpr int kMaxBlocks = 16;
+constexpr int kMaxBlocks = ONGYM_MAX_BLOCKS;
 
 // LDS behind the state block: row u64[kMaxRowWords] | start u16[kMaxMods][kMaxBlocks] | length u16[kMaxMods][kMaxBlocks] |
 // count i32[kMaxMods]

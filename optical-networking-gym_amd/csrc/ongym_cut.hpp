@@ -31,7 +31,7 @@
 
 namespace ongym {
 
-constexpr int kCutLinks = 13;             // cut_out doubles per replica: set_out's twelve, dropped
+constexpr int kCutLinks = ONGYM_N_CUT_LINKS;   // cut_out doubles per replica: set_out's twelve, dropped
 
 __host__ __device__ inline size_t cut_lds_bytes(const Params &P) {
     return (lds_bytes(P) + (size_t)P.capacity * (P.track_ids ? 26 : 14) + 15) & ~(size_t)15;

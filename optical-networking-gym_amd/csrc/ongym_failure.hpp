@@ -28,7 +28,7 @@
 
 namespace ongym {
 
-constexpr int kFailureImpact = 10;        // link_out doubles per (replica, failed link)
+constexpr int kFailureImpact = ONGYM_N_FAILURE_IMPACT;   // link_out doubles per (replica, failed link)
 
 __host__ __device__ inline size_t failure_lds_bytes(const Params &P) {
     return (lds_bytes(P) + (size_t)P.capacity * (P.track_ids ? 10 : 6) + 15) & ~(size_t)15;
@@ -188,8 +188,8 @@ __global__ __launch_bounds__(64) void k_failure_impact(const Params *__restrict_
 // the set, a route is eligible if its mask does not; and the row has two more columns (lost_no_route, failed_links).  Same LDS
 // layout (failure_lds_bytes), same loop bounds.  It is a kernel of its own, not a second instantiation of one templated body:
 // with the body shared, k_failure_impact kept its VGPRs and occupancy but spilled 26-28 SGPRs instead of 18-20.
-constexpr int kFailureSets = 12;          // set_out doubles per (replica, link set): link_out's ten, lost_no_route, failed_links
-constexpr int kMaxFailureSets = 65535;    // link sets per replica: the grid's y extent
+constexpr int kFailureSets = ONGYM_N_FAILURE_SETS;        // set_out doubles per (replica, link set): link_out's ten, lost_no_route, failed_links
+constexpr int kMaxFailureSets = ONGYM_MAX_FAILURE_SETS;   // link sets per replica: the grid's y extent
 
 // a set is evaluated if it is not empty and has no bit at an index >= E
 __device__ __forceinline__ bool failure_set_valid(int E, uint64_t f0, uint64_t f1) {

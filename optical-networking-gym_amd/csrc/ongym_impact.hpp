@@ -36,8 +36,8 @@
 
 namespace ongym {
 
-constexpr int kActionImpact = 8;          // impact_out doubles per (replica, action)
-constexpr int kMaxImpactActions = 256;
+constexpr int kActionImpact = ONGYM_N_ACTION_IMPACT;   // impact_out doubles per (replica, action)
+constexpr int kMaxImpactActions = ONGYM_MAX_IMPACT_ACTIONS;
 
 __host__ __device__ inline size_t impact_lds_bytes(const Params &P) {
     return (lds_bytes(P) + 192 + (size_t)P.capacity * 8 + 15) & ~(size_t)15;

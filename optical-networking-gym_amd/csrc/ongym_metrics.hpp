@@ -18,8 +18,8 @@
 
 namespace ongym {
 
-constexpr int kLinkMetrics = 8;   // link_out floats per link
-constexpr int kLinkStats = 4;     // link_stats doubles per link
+constexpr int kLinkMetrics = ONGYM_N_LINK_METRICS;   // link_out floats per link
+constexpr int kLinkStats = ONGYM_N_LINK_STATS;       // link_stats doubles per link
 
 __host__ __device__ inline size_t metrics_lds_bytes(const Params &P) { return (size_t)P.n_links * P.row_words * 8; }
 

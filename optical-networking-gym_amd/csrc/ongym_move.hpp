@@ -33,7 +33,7 @@
 
 namespace ongym {
 
-constexpr int kMoveOut = 6;               // move_out doubles per (replica, move)
+constexpr int kMoveOut = ONGYM_N_MOVE_COLUMNS;   // move_out doubles per (replica, move)
 
 __host__ __device__ inline size_t move_lds_bytes(const Params &P) {
     return (lds_bytes(P) + (size_t)P.capacity / 8 + 15) & ~(size_t)15;      // capacity % 64 == 0

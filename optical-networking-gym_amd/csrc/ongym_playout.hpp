@@ -25,11 +25,11 @@
 
 namespace ongym {
 
-constexpr int kPlayout = 8;               // playout_out doubles per (replica, action, sample)
-constexpr int kMaxPlayoutActions = 256;
-constexpr int kMaxPlayoutSamples = 64;
-constexpr int kMaxPlayoutScenarios = 4096;   // A * R per replica: the second grid dimension when replicas are fastest
-constexpr int kMaxPlayoutHorizon = 4096;
+constexpr int kPlayout = ONGYM_N_PLAYOUT;   // playout_out doubles per (replica, action, sample)
+constexpr int kMaxPlayoutActions = ONGYM_MAX_PLAYOUT_ACTIONS;
+constexpr int kMaxPlayoutSamples = ONGYM_MAX_PLAYOUT_SAMPLES;
+constexpr int kMaxPlayoutScenarios = ONGYM_MAX_PLAYOUT_SCENARIOS;   // A * R per replica: the second grid dimension when replicas are fastest
+constexpr int kMaxPlayoutHorizon = ONGYM_MAX_PLAYOUT_HORIZON;
 
 template <bool UA, bool R32, int POLICY>
 __device__ __forceinline__ int playout_policy(Ctx &c, Choice &ch) {

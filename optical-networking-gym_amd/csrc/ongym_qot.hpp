@@ -20,9 +20,9 @@
 
 namespace ongym {
 
-constexpr int kServiceQot = 4;   // svc_out doubles per record: GSNR, ASE, NLI (dB), margin
-constexpr int kReplicaQot = 6;   // replica_out doubles per replica
-constexpr int kLinkQot = 3;      // link_out floats per link
+constexpr int kServiceQot = ONGYM_N_SERVICE_QOT;   // svc_out doubles per record: GSNR, ASE, NLI (dB), margin
+constexpr int kReplicaQot = ONGYM_N_REPLICA_QOT;   // replica_out doubles per replica
+constexpr int kLinkQot = ONGYM_N_LINK_QOT;         // link_out floats per link
 
 // LDS: the state block | lim0 f64[8] | link count u32[E] | link below count u32[E] | link min-margin key u32[E]
 __host__ __device__ inline size_t qot_lds_bytes(const Params &P) {

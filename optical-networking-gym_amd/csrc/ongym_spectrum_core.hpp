@@ -9,6 +9,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "../../include/ongym.h"
+
 #ifdef __HIPCC__
 #define ONGYM_SPECTRUM_HD __host__ __device__ inline
 #else
@@ -17,10 +19,10 @@
 
 namespace ongym {
 
-constexpr int kSpectrumAudit = 10;          // audit_out entries per replica
-constexpr int kSpectrumRec = 6;             // rec_out entries per record
-constexpr int kSpectrumMaxOwners = 32766;   // owner_out: a guard cell of record i reads -2 - i >= -32767
-constexpr int kOwnerFree = -1, kOwnerUnowned = -32768;
+constexpr int kSpectrumAudit = ONGYM_N_SPECTRUM_AUDIT_COLUMNS;   // audit_out entries per replica
+constexpr int kSpectrumRec = ONGYM_N_SPECTRUM_RECORD_COLUMNS;    // rec_out entries per record
+constexpr int kSpectrumMaxOwners = ONGYM_MAX_OWNER_CAPACITY;     // owner_out: a guard cell of record i reads -2 - i >= -32767
+constexpr int kOwnerFree = ONGYM_OWNER_FREE, kOwnerUnowned = ONGYM_OWNER_UNOWNED;
 
 struct SpectrumRec { int path, slot, n, mod; };
 

@@ -17,12 +17,13 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC_DIR = os.path.join(os.path.dirname(PKG_DIR), "csrc")
 HIP_LIB_PATH = os.path.join(CSRC_DIR, "libongym_hip.so")
 
+OK, E_ARG, E_HIP, E_STATE, E_CAPACITY, E_LIMIT = 0, -1, -2, -3, -4, -5   # return codes (ONGYM_OK, ONGYM_E_*)
 POLICY_FIRST_FIT = 0
 POLICY_LOAD_BALANCING = 1
 POLICY_HIGHEST_SNR = 2
 POLICY_LOWEST_SPECTRUM, POLICY_LB_FIRST_FIT, POLICY_BEST_MOD_LB = 3, 4, 5
 POLICY_MSCL_SIMPLIFIED, POLICY_MSCL_SEQUENTIAL, POLICY_PSR, POLICY_EXACT_FIT = 6, 7, 8, 9
-POLICY_LOWEST_FRAGMENTATION, POLICY_MSCL = 10, 11
+POLICY_LOWEST_FRAGMENTATION, POLICY_MSCL, POLICY_COUNT = 10, 11, 12
 F_BLOCKED_RESOURCES, F_BLOCKED_OSNR, F_QOT_ERROR, F_OVERFLOW, F_NO_REQUEST = 1, 2, 4, 8, 16
 DTYPE_F32, DTYPE_BF16 = 0, 1                                # ongym_masked_categorical logits dtypes
 HEAD_SAMPLE, HEAD_ARGMAX, HEAD_EVALUATE = 0, 1, 2           # ... and modes
@@ -54,11 +55,11 @@ OWNER_FREE, OWNER_GUARD_BASE, OWNER_UNOWNED = -1, -2, -32768  # ... owner_out: f
 MAX_OWNER_CAPACITY = 32766                                  # ... owner_out needs capacity <= this
 ADMISSION_MAP = ("status", "admitted", "blocked_no_spectrum", "blocked_qot", "blocking_probability", "bit_rate_blocking",
                  "lowest_margin", "detoured")                # ongym_admission_map: summary_out entries per (replica, action)
-MAX_ADMISSION_RATES = 16                                    # ... and the longest rate list
+MAX_ADMISSION_ACTIONS, MAX_ADMISSION_RATES = 256, 16        # ... and the longest action and rate lists
 PLAYOUT = ("status", "first_accepted", "steps", "accepted", "blocked", "bit_rate_accepted", "bit_rate_requested",
            "active_end")                                    # ongym_playout: playout_out entries per (replica, action, sample)
 PLAYOUT_OWN_STREAM = 1                                      # ... its flag: the replica's own source continues
-MAX_PLAYOUT_SAMPLES, MAX_PLAYOUT_SCENARIOS, MAX_PLAYOUT_HORIZON = 64, 4096, 4096   # ... and its limits (R, A R, H)
+MAX_PLAYOUT_ACTIONS, MAX_PLAYOUT_SAMPLES, MAX_PLAYOUT_SCENARIOS, MAX_PLAYOUT_HORIZON = 256, 64, 4096, 4096   # ... its limits (A, R, A R, H)
 
 _i32p, _f64p = C.POINTER(C.c_int32), C.POINTER(C.c_double)
 
@@ -221,133 +222,93 @@ class ConfigHolder:
         return c.k_paths * c.n_mods_consider * c.n_slots
 
 
+# ongym_sizeof(what), what = 0..5: the struct and the size this module lays it out with
+STRUCT_SIZES = (("ongym_config", C.sizeof(OngymConfig)), ("ongym_request", REQUEST_DTYPE.itemsize),
+                ("ongym_step_rec", STEP_DTYPE.itemsize), ("ongym_service", SERVICE_DTYPE.itemsize),
+                ("ongym_stats", STATS_DTYPE.itemsize), ("ongym_move", MOVE_DTYPE.itemsize))
+
+# The prototypes of include/ongym.h in the header's order, name -> (restype, argtypes): a new entry point is its prototype
+# there and one row here (tests/test_abi_mirror_host.py holds the two together).  Pointers are c_void_p, because callers pass
+# arr.ctypes.data, None and c_void_p, except the three that are passed by reference.
+_i32, _u32, _i64, _u64, _f32, _f64, _vp = C.c_int32, C.c_uint32, C.c_int64, C.c_uint64, C.c_float, C.c_double, C.c_void_p
+SIGNATURES = {
+    "ongym_create": (_i32, (C.POINTER(OngymConfig), C.POINTER(_vp))),
+    "ongym_destroy": (None, (_vp,)),
+    "ongym_seed": (_i32, (_vp, _u64)),
+    "ongym_seed_base": (_i32, (_vp, _u64, _u64)),
+    "ongym_set_requests": (_i32, (_vp, _vp, _i64)),
+    "ongym_reset": (_i32, (_vp, _vp)),
+    "ongym_reset_episode_counters": (_i32, (_vp, _vp)),
+    "ongym_step_policy": (_i32, (_vp, _i32, _i32, _vp)),
+    "ongym_step_actions": (_i32, (_vp, _vp, _vp)),
+    "ongym_step_actions_bundle": (_i32, (_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp)),
+    "ongym_policy_actions": (_i32, (_vp, _i32, _vp, _vp)),
+    "ongym_observe": (_i32, (_vp, _vp, _vp)),
+    "ongym_observe_blocks": (_i32, (_vp, _i32, _vp, _vp, _vp)),
+    "ongym_link_metrics": (_i32, (_vp, _vp, _vp, _vp)),
+    "ongym_service_qot": (_i32, (_vp, _vp, _vp, _vp)),
+    "ongym_action_impact": (_i32, (_vp, _i32, _vp, _vp, _vp)),
+    "ongym_failure_impact": (_i32, (_vp, _i32, _vp, _vp, _vp)),
+    "ongym_failure_sets": (_i32, (_vp, _i32, _vp, _i32, _vp, _vp)),
+    "ongym_cut_links": (_i32, (_vp, _vp, _i32, _i32, _vp, _vp, _vp)),
+    "ongym_repair_links": (_i32, (_vp, _vp, _i32, _vp)),
+    "ongym_failed_links": (_i32, (_vp, _vp)),
+    "ongym_spectrum_map": (_i32, (_vp, _vp, _vp, _vp, _vp)),
+    "ongym_move_services": (_i32, (_vp, _i32, _vp, _i32, _vp)),
+    "ongym_admission_map": (_i32, (_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp)),
+    "ongym_playout": (_i32, (_vp, _i32, _vp, _i32, _i32, _i32, _u64, _i32, _vp)),
+    "ongym_sample_actions": (_i32, (_vp, _vp, _u64, _u64, _vp)),
+    "ongym_masked_categorical": (_i32, (_vp, _vp, _i32, _vp, _i32, _u64, _u64, _vp, _vp, _vp, _vp, _vp)),
+    "ongym_masked_categorical_backward": (_i32, (_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp)),
+    "ongym_masked_categorical_rows": (_i32, (_vp, _i32, _vp, _i32, _vp, _i32, _i32, _u64, _u64, _vp, _vp, _vp, _vp, _vp)),
+    "ongym_masked_categorical_backward_rows": (_i32, (_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp)),
+    "ongym_gae": (_i32, (_vp, _i32, _vp, _vp, _vp, _f32, _f32, _vp, _vp)),
+    "ongym_query_available": (_i32, (_vp, _i32, _i32, _vp)),
+    "ongym_query_gsnr": (_i32, (_vp, _i32, _i32, _i32, _i32, _vp)),
+    "ongym_query_gsnr_many": (_i32, (_vp, _i32, _i32, _vp, _vp)),
+    "ongym_query_candidates": (_i32, (_vp, _vp, _i32, _i32, _vp, _vp)),
+    "ongym_query_path_free": (_i32, (_vp, _i32, _i32, _i32, _i32, _vp)),
+    "ongym_query_moves": (_i32, (_vp, _i32, _vp, _vp)),
+    "ongym_query_grid": (_i32, (_vp, _i32, _vp)),
+    "ongym_query_services": (_i32, (_vp, _i32, _vp, _vp)),
+    "ongym_query_request": (_i32, (_vp, _i32, _vp)),
+    "ongym_stats_get": (_i32, (_vp, _vp)),
+    "ongym_state_size": (_i32, (_vp, _i32, C.POINTER(_i64))),
+    "ongym_state_save": (_i32, (_vp, _i32, _vp, _vp)),
+    "ongym_state_load": (_i32, (_vp, _i32, _vp, _vp, _i32)),
+    "ongym_fork": (_i32, (_vp, _vp, _i32)),
+    "ongym_query_occupancy": (_i32, (_vp, _vp, _vp, _vp)),
+    "ongym_query_occupancy_policy": (_i32, (_vp, _i32, _vp, _vp, _vp)),
+    "ongym_query_link_weight_entry": (_i32, (_vp, _i32, _u32, _vp, _vp)),
+    "ongym_query_path_rows": (_i32, (_vp, _i32, _vp)),
+    "ongym_sync": (_i32, (_vp,)),
+    "ongym_set_stream": (_i32, (_vp, _vp, _i32)),
+    "ongym_last_kernel_ms": (_f64, (_vp,)),
+    "ongym_last_error": (C.c_char_p, (_vp,)),
+    "ongym_abi_version": (_i32, ()),
+    "ongym_sizeof": (_i32, (_i32,)),
+}
+EXPORTED_SYMBOLS = tuple(SIGNATURES)
+# An older build of the library named by ONGYM_HIP_LIB (tools/ab_bench.py, tools/time_action_impact.py --fork-loop, the
+# diag_stamps tools) may lack these; calling one then fails with ctypes' AttributeError.  Any other missing name fails the load.
+ABSENT_FROM_OLDER_BUILDS = (
+    "ongym_step_actions_bundle", "ongym_action_impact", "ongym_failure_impact", "ongym_failure_sets", "ongym_cut_links",
+    "ongym_repair_links", "ongym_failed_links", "ongym_move_services", "ongym_spectrum_map", "ongym_admission_map",
+    "ongym_playout", "ongym_sample_actions", "ongym_query_link_weight_entry", "ongym_query_path_rows", "ongym_set_stream")
+
 _LIB = None
 
 
 def _declare(lib):
-    vp = C.c_void_p
-    lib.ongym_create.argtypes = [C.POINTER(OngymConfig), C.POINTER(vp)]
-    lib.ongym_destroy.argtypes = [vp]
-    lib.ongym_destroy.restype = None
-    lib.ongym_seed.argtypes = [vp, C.c_uint64]
-    lib.ongym_seed_base.argtypes = [vp, C.c_uint64, C.c_uint64]
-    lib.ongym_set_requests.argtypes = [vp, vp, C.c_int64]
-    lib.ongym_reset.argtypes = [vp, vp]
-    lib.ongym_reset_episode_counters.argtypes = [vp, vp]
-    lib.ongym_step_policy.argtypes = [vp, C.c_int32, C.c_int32, vp]
-    lib.ongym_step_actions.argtypes = [vp, vp, vp]
-    lib.ongym_policy_actions.argtypes = [vp, C.c_int32, vp, vp]
-    if hasattr(lib, "ongym_step_actions_bundle"):
-        lib.ongym_step_actions_bundle.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, vp]
-        lib.ongym_step_actions_bundle.restype = C.c_int32
-    lib.ongym_observe.argtypes = [vp, vp, vp]
-    lib.ongym_observe_blocks.argtypes = [vp, C.c_int32, vp, vp, vp]
-    lib.ongym_observe_blocks.restype = C.c_int32
-    lib.ongym_link_metrics.argtypes = [vp, vp, vp, vp]
-    lib.ongym_link_metrics.restype = C.c_int32
-    lib.ongym_service_qot.argtypes = [vp, vp, vp, vp]
-    lib.ongym_service_qot.restype = C.c_int32
-    if hasattr(lib, "ongym_action_impact"):     # (tools/time_action_impact.py --fork-loop times an older build through ONGYM_HIP_LIB)
-        lib.ongym_action_impact.argtypes = [vp, C.c_int32, vp, vp, vp]
-        lib.ongym_action_impact.restype = C.c_int32
-    if hasattr(lib, "ongym_failure_impact"):    # (an older build named by ONGYM_HIP_LIB has none)
-        lib.ongym_failure_impact.argtypes = [vp, C.c_int32, vp, vp, vp]
-        lib.ongym_failure_impact.restype = C.c_int32
-    if hasattr(lib, "ongym_failure_sets"):      # (an older build named by ONGYM_HIP_LIB has none)
-        lib.ongym_failure_sets.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp]
-        lib.ongym_failure_sets.restype = C.c_int32
-    if hasattr(lib, "ongym_cut_links"):         # (an older build named by ONGYM_HIP_LIB has none)
-        lib.ongym_cut_links.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, vp]
-        lib.ongym_cut_links.restype = C.c_int32
-        lib.ongym_repair_links.argtypes = [vp, vp, C.c_int32, vp]
-        lib.ongym_repair_links.restype = C.c_int32
-        lib.ongym_failed_links.argtypes = [vp, vp]
-        lib.ongym_failed_links.restype = C.c_int32
-    if hasattr(lib, "ongym_move_services"):     # (an older build named by ONGYM_HIP_LIB has none)
-        lib.ongym_move_services.argtypes = [vp, C.c_int32, vp, C.c_int32, vp]
-        lib.ongym_move_services.restype = C.c_int32
-    if hasattr(lib, "ongym_spectrum_map"):      # (an older build named by ONGYM_HIP_LIB has none)
-        lib.ongym_spectrum_map.argtypes = [vp, vp, vp, vp, vp]
-        lib.ongym_spectrum_map.restype = C.c_int32
-    if hasattr(lib, "ongym_admission_map"):     # (an older build named by ONGYM_HIP_LIB has none)
-        lib.ongym_admission_map.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp]
-        lib.ongym_admission_map.restype = C.c_int32
-    if hasattr(lib, "ongym_playout"):           # (an older build named by ONGYM_HIP_LIB has none)
-        lib.ongym_playout.argtypes = [vp, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, vp]
-        lib.ongym_playout.restype = C.c_int32
-    if hasattr(lib, "ongym_sample_actions"):
-        lib.ongym_sample_actions.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp]
-        lib.ongym_sample_actions.restype = C.c_int32
-    lib.ongym_masked_categorical.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, C.c_uint64, C.c_uint64, vp, vp, vp, vp, vp]
-    lib.ongym_masked_categorical.restype = C.c_int32
-    lib.ongym_masked_categorical_backward.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
-    lib.ongym_masked_categorical_backward.restype = C.c_int32
-    lib.ongym_masked_categorical_rows.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64,
-                                                  vp, vp, vp, vp, vp]
-    lib.ongym_masked_categorical_rows.restype = C.c_int32
-    lib.ongym_masked_categorical_backward_rows.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
-    lib.ongym_masked_categorical_backward_rows.restype = C.c_int32
-    lib.ongym_gae.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_float, C.c_float, vp, vp]
-    lib.ongym_gae.restype = C.c_int32
-    lib.ongym_state_size.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64)]
-    lib.ongym_state_size.restype = C.c_int32
-    lib.ongym_state_save.argtypes = [vp, C.c_int32, vp, vp]
-    lib.ongym_state_save.restype = C.c_int32
-    lib.ongym_state_load.argtypes = [vp, C.c_int32, vp, vp, C.c_int32]
-    lib.ongym_state_load.restype = C.c_int32
-    lib.ongym_fork.argtypes = [vp, vp, C.c_int32]
-    lib.ongym_fork.restype = C.c_int32
-    lib.ongym_query_available.argtypes = [vp, C.c_int32, C.c_int32, vp]
-    lib.ongym_query_gsnr.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]
-    lib.ongym_query_gsnr_many.argtypes = [vp, C.c_int32, C.c_int32, vp, vp]
-    lib.ongym_query_moves.argtypes = [vp, C.c_int32, vp, vp]
-    lib.ongym_query_grid.argtypes = [vp, C.c_int32, vp]
-    lib.ongym_query_candidates.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp]
-    lib.ongym_query_path_free.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]
-    lib.ongym_query_services.argtypes = [vp, C.c_int32, vp, vp]
-    lib.ongym_query_request.argtypes = [vp, C.c_int32, vp]
-    lib.ongym_stats_get.argtypes = [vp, vp]
-    lib.ongym_query_occupancy.argtypes = [vp, vp, vp, vp]
-    if hasattr(lib, "ongym_query_link_weight_entry"):       # (absent from an older build named by ONGYM_HIP_LIB)
-        lib.ongym_query_link_weight_entry.argtypes = [vp, C.c_int32, C.c_uint32, vp, vp]
-        lib.ongym_query_link_weight_entry.restype = C.c_int32
-    if hasattr(lib, "ongym_query_path_rows"):
-        lib.ongym_query_path_rows.argtypes = [vp, C.c_int32, vp]
-        lib.ongym_query_path_rows.restype = C.c_int32
-    if os.environ.get("ONGYM_HIP_LIB") and not hasattr(lib, "ongym_query_occupancy_policy"):
-        # an older experiment build named by ONGYM_HIP_LIB (tools/ab_bench.py): first fit only
-        lib.ongym_query_occupancy_policy = lambda h, policy, nb, lds, lean: lib.ongym_query_occupancy(h, nb, lds, lean)
-        return _declare_tail(lib, vp, skip=("ongym_query_occupancy_policy",))
-    lib.ongym_query_occupancy_policy.argtypes = [vp, C.c_int32, vp, vp, vp]
-    _declare_tail(lib, vp)
-
-
-def _declare_tail(lib, vp, skip=()):
-    lib.ongym_sync.argtypes = [vp]
-    if hasattr(lib, "ongym_set_stream"):
-        lib.ongym_set_stream.argtypes = [vp, vp, C.c_int32]
-        lib.ongym_set_stream.restype = C.c_int32
-    lib.ongym_last_kernel_ms.argtypes = [vp]
-    lib.ongym_last_kernel_ms.restype = C.c_double
-    lib.ongym_last_error.argtypes = [vp]
-    lib.ongym_last_error.restype = C.c_char_p
-    lib.ongym_abi_version.argtypes = []
-    lib.ongym_sizeof.argtypes = [C.c_int32]
-    for name in ("ongym_create", "ongym_seed", "ongym_seed_base", "ongym_set_requests", "ongym_reset", "ongym_reset_episode_counters", "ongym_step_policy",
-                 "ongym_step_actions", "ongym_policy_actions", "ongym_observe", "ongym_query_available", "ongym_query_gsnr", "ongym_query_gsnr_many", "ongym_query_moves",
-                 "ongym_query_grid", "ongym_query_services", "ongym_query_request", "ongym_stats_get", "ongym_sync",
-                 "ongym_abi_version", "ongym_sizeof", "ongym_query_candidates", "ongym_query_path_free", "ongym_observe", "ongym_query_occupancy", "ongym_query_occupancy_policy"):
-        if name not in skip:
-            getattr(lib, name).restype = C.c_int32
-
-
-EXPORTED_SYMBOLS = (
-    "ongym_create", "ongym_destroy", "ongym_seed", "ongym_seed_base", "ongym_set_requests", "ongym_reset", "ongym_reset_episode_counters", "ongym_step_policy",
-    "ongym_step_actions", "ongym_step_actions_bundle", "ongym_policy_actions", "ongym_observe", "ongym_observe_blocks", "ongym_link_metrics", "ongym_service_qot", "ongym_action_impact", "ongym_failure_impact", "ongym_failure_sets", "ongym_cut_links", "ongym_repair_links", "ongym_failed_links", "ongym_move_services", "ongym_spectrum_map", "ongym_admission_map", "ongym_playout", "ongym_sample_actions", "ongym_masked_categorical", "ongym_masked_categorical_backward",
-    "ongym_masked_categorical_rows", "ongym_masked_categorical_backward_rows", "ongym_gae", "ongym_state_size", "ongym_state_save", "ongym_state_load", "ongym_fork", "ongym_query_available", "ongym_query_gsnr", "ongym_query_gsnr_many", "ongym_query_moves", "ongym_query_grid",
-    "ongym_query_services", "ongym_query_request", "ongym_query_candidates", "ongym_query_path_free",
-    "ongym_stats_get", "ongym_sync", "ongym_set_stream", "ongym_last_kernel_ms", "ongym_query_occupancy", "ongym_query_occupancy_policy",
-    "ongym_query_link_weight_entry", "ongym_query_path_rows", "ongym_last_error", "ongym_abi_version", "ongym_sizeof")
+    for name, (restype, argtypes) in SIGNATURES.items():
+        if hasattr(lib, name):
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, list(argtypes)
+        elif name == "ongym_query_occupancy_policy" and os.environ.get("ONGYM_HIP_LIB"):
+            # an older experiment build named by ONGYM_HIP_LIB (tools/ab_bench.py): first fit only
+            lib.ongym_query_occupancy_policy = lambda h, policy, nb, lds, lean: lib.ongym_query_occupancy(h, nb, lds, lean)
+        elif name not in ABSENT_FROM_OLDER_BUILDS:
+            raise RuntimeError(f"{lib._name} does not export {name}")
 
 
 def load_library(path: Optional[str] = None):
@@ -364,11 +325,9 @@ def load_library(path: Optional[str] = None):
     _declare(lib)
     if lib.ongym_abi_version() != ABI_VERSION:
         raise RuntimeError("libongym_hip.so ABI version mismatch")
-    sizes = (C.sizeof(OngymConfig), REQUEST_DTYPE.itemsize, STEP_DTYPE.itemsize, SERVICE_DTYPE.itemsize,
-             STATS_DTYPE.itemsize, MOVE_DTYPE.itemsize)
-    for what, expect in enumerate(sizes):
+    for what, (struct, expect) in enumerate(STRUCT_SIZES):
         got = lib.ongym_sizeof(what)
         if got != expect:
-            raise RuntimeError(f"struct size mismatch for #{what}: library {got}, python {expect}")
+            raise RuntimeError(f"struct size mismatch for {struct}: library {got}, python {expect}")
     _LIB = lib
     return lib

@@ -52,7 +52,7 @@ class BatchedQRMSAEnv:
         self.lib = nat.load_library()
         h = C.c_void_p()
         rc = self.lib.ongym_create(C.byref(self.holder.struct), C.byref(h))
-        if rc != 0:
+        if rc != nat.OK:
             raise OngymError(f"ongym_create failed ({rc}): {self.lib.ongym_last_error(None).decode()}")
         self._h = h
         self._trace = None
@@ -71,7 +71,7 @@ class BatchedQRMSAEnv:
             pass
 
     def _check(self, rc: int, what: str):
-        if rc != 0:
+        if rc != nat.OK:
             raise OngymError(f"{what} failed ({rc}): {self.lib.ongym_last_error(self._h).decode()}")
 
     @staticmethod
