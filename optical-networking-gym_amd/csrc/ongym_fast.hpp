@@ -241,6 +241,10 @@ __device__ __forceinline__ void lds_or_lanes(uint64_t mask, uint32_t addr, uint3
     uint64_t saved;
     asm volatile("s_and_saveexec_b64 %0, %1\n\tds_or_b32 %2, %3\n\ts_mov_b64 exec, %0" : "=&s"(saved) : "s"(mask), "v"(addr), "v"(val) : "memory", "scc");
 }
+__device__ __forceinline__ void lds_write16_lanes(uint64_t mask, uint32_t addr, uint32_t val) {     // the low halfword of `val`
+    uint64_t saved;
+    asm volatile("s_and_saveexec_b64 %0, %1\n\tds_write_b16 %2, %3\n\ts_mov_b64 exec, %0" : "=&s"(saved) : "s"(mask), "v"(addr), "v"(val) : "memory", "scc");
+}
 __device__ __forceinline__ void lds_and2_lanes(uint64_t mask, uint32_t addr, uint32_t v0, uint32_t v1) {
     uint64_t saved;
     asm volatile("s_and_saveexec_b64 %0, %1\n\tds_and_b32 %2, %3\n\tds_and_b32 %2, %4 offset:4\n\ts_mov_b64 exec, %0" : "=&s"(saved) : "s"(mask), "v"(addr), "v"(v0), "v"(v1) : "memory", "scc");
@@ -732,6 +736,12 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
         asm volatile("" : "+s"(active));        // decided where it is used: held from the top of a step, the answer costs a register pair
         return active <= four_max;
     };
+    // The stores of the straight form as one statement each (lds_write16_lanes): EXEC masks the store alone, the two v_mbcnt and the
+    // address run on every lane, and no `s_cbranch_execz` skips an empty chunk (the compiler's `if (ov)` gets one from chunk 2 on;
+    // three of them lie on a request's common path).  First fit without records and with one mask word: the kernels that were
+    // measured ("Scalar issue slots of a request"); the others keep their code.
+    constexpr bool kListAsm = kFfHints && LIST_TAIL;
+    const uint32_t list_base = lds_addr(list);
     int ep_len = P.episode_length;          // held in a scalar register (the lean units are built without loop-invariant code motion)
     asm volatile("" : "+s"(ep_len));
     const char __attribute__((address_space(1))) *const tab = (const char __attribute__((address_space(1))) *)P.pair_tab2k;
@@ -1063,7 +1073,8 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                         if (M64) ov |= ((ab[c].y >> 23) & mask_hi) != 0;
                         const uint64_t bal = __ballot(ov);
                         const int p = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, (uint32_t)L));
-                        if (ov) list[p] = (uint16_t)(c * kWave + lane);
+                        if constexpr (kListAsm) lds_write16_lanes(bal, list_base + 2u * (uint32_t)p, (uint32_t)(c * kWave + lane));
+                        else if (ov) list[p] = (uint16_t)(c * kWave + lane);
                         L += __popcll((unsigned long long)bal);
                     }
                     // The tail: records 256 and up, one chunk per compare of the running count, positions continuing from L (the
@@ -1076,7 +1087,8 @@ __device__ __forceinline__ void fast_run(const Params &P, int nsteps, ongym_step
                             const bool ov = (rec[c * kWave + lane].x & mask_lo) != 0;
                             const uint64_t bal = __ballot(ov);
                             const int p = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, (uint32_t)L));
-                            if (ov) list[p] = (uint16_t)(c * kWave + lane);
+                            if constexpr (kListAsm) lds_write16_lanes(bal, list_base + 2u * (uint32_t)p, (uint32_t)(c * kWave + lane));
+                            else if (ov) list[p] = (uint16_t)(c * kWave + lane);
                             L += __popcll((unsigned long long)bal);
                         }
                     }
