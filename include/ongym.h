@@ -904,6 +904,9 @@ const char *ongym_last_error(ongym_env *env);
 int32_t ongym_abi_version(void);
 int32_t ongym_sizeof(int32_t what); /* 0 config, 1 request, 2 step_rec, 3 service, 4 stats, 5 move */
 
+/* The weighted candidate-scoring policy, weights per replica: the call, its features and its rules */
+#include "ongym_score.h"
+
 #ifdef __cplusplus
 }
 #endif

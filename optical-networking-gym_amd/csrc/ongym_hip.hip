@@ -34,6 +34,7 @@
 #include "ongym_move.hpp"          // running lightpaths moved on live replicas (ongym_move_services)
 #include "ongym_admission.hpp"     // first-fit admission of every node pair and bit rate (ongym_admission_map)
 #include "ongym_playout.hpp"       // candidate actions followed by H policy steps on a private copy (ongym_playout)
+#include "ongym_score.hpp"         // weighted candidate scoring, weights per replica (ongym_score_actions)
 
 using namespace ongym;
 
@@ -1846,6 +1847,33 @@ int ongym_policy_actions(ongym_env *env, int32_t policy, int32_t *actions, uint8
     Span sp[] = {{actions, B * sizeof(int32_t), kOut}, {flags, B, kOut}};
     if ((rc = stage_open(env, env->stage[kStagePolicy], sp))) return rc;
     rc = launch_run(env, kModePolicyOnly, policy, 1, nullptr, sp[0].as<int32_t>(), sp[1].as<uint8_t>(), nullptr);
+    return rc ? rc : stage_close(env, sp);
+}
+
+int ongym_score_actions(ongym_env *env, const double *weights, int32_t per_replica, int32_t *actions, double *best_out,
+                        int32_t *count_out) {
+    if (!env) return ONGYM_E_ARG;
+    if (!actions || !weights) return fail_arg(env, "null actions/weights");
+    const Params &P = env->P;
+    if (P.n_mods_consider < P.n_mods)
+        return fail_arg(env, "scoring walks every format: it needs modulations_to_consider == n_mods");
+    const size_t lds = score_lds_bytes(P);
+    if (lds > 160 * 1024) return fail_arg(env, "the scoring kernel's LDS block exceeds 160 KiB: lower capacity", ONGYM_E_LIMIT);
+    const size_t B = (size_t)P.batch, nw = (per_replica ? B : 1) * kScoreFeatures;
+    if (!env->cfg.io_device)
+        for (size_t i = 0; i < nw; i++)
+            if (!std::isfinite(weights[i])) return fail_arg(env, "weights must be finite");
+    HIP_TRY(env, hipSetDevice(env->cfg.device));
+    Span sp[] = {{actions, B * sizeof(int32_t), kOut}, {best_out, B * (1 + kScoreFeatures) * sizeof(double), kOut},   // staging:
+                 {count_out, B * kScoreCounts * sizeof(int32_t), kOut}, {weights, nw * sizeof(double), kIn}};        // actions | best_out | count_out | weights
+    int rc;
+    if ((rc = stage_open(env, env->stage[kStageScore], sp))) return rc;
+    rc = timed_launch(env, [&] {
+        return with_layout(P, [&](auto UA, auto R32) {     // the step kernels' (UA, R32): the same QoT decisions
+            return launch_lds(env, k_score_actions<UA, R32>, dim3(P.batch), lds, env->d_P, sp[3].as<const double>(),
+                              (int)(per_replica != 0), sp[0].as<int32_t>(), sp[1].as<double>(), sp[2].as<int32_t>());
+        });
+    });
     return rc ? rc : stage_close(env, sp);
 }
 

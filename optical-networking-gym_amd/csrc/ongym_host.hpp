@@ -27,6 +27,7 @@ enum {
     kStageQuery,    // the ongym_query_* calls: used with io_device too (query results are always host buffers)
     kStageMove,     // ongym_move_services: move_out | moves
     kStageSpectrum, // ongym_spectrum_map: owner_out | rec_out | release_out | audit_out
+    kStageScore,    // ongym_score_actions: actions | best_out | count_out | weights
     kStages
 };
 

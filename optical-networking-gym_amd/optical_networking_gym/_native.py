@@ -60,6 +60,38 @@ PLAYOUT = ("status", "first_accepted", "steps", "accepted", "blocked", "bit_rate
            "active_end")                                    # ongym_playout: playout_out entries per (replica, action, sample)
 PLAYOUT_OWN_STREAM = 1                                      # ... its flag: the replica's own source continues
 MAX_PLAYOUT_ACTIONS, MAX_PLAYOUT_SAMPLES, MAX_PLAYOUT_SCENARIOS, MAX_PLAYOUT_HORIZON = 256, 64, 4096, 4096   # ... its limits (A, R, A R, H)
+# ongym_score_actions (include/ongym_score.h): the features x0..x9 of a candidate placement, in the order of the weights
+SCORE_FEATURES = ("route", "hops", "format_rank", "slots", "slot_hops", "start", "load", "touch", "gsnr", "margin")
+SCORE_COUNT_COLUMNS = ("with_spectrum", "feasible", "flags")   # ... and count_out entries per replica
+
+
+def score_weights(**named) -> np.ndarray:
+    """float64 [len(SCORE_FEATURES)]: the weight vector with the named features' weights, zero elsewhere"""
+    w = np.zeros(len(SCORE_FEATURES))
+    for name, value in named.items():
+        w[SCORE_FEATURES.index(name)] = float(value)
+    return w
+
+
+def first_feasible_weights(n_mods: int, n_slots: int) -> np.ndarray:
+    """The weights whose score is the step's action index k M S + format_rank S + start: the lowest feasible action wins"""
+    return score_weights(route=int(n_mods) * int(n_slots), format_rank=int(n_slots), start=1)
+
+
+# Weight vectors by name.  first_feasible depends on the configuration: its entry is the helper, called with (n_mods, n_slots).
+SCORE_PRESETS = {
+    "first_feasible": first_feasible_weights,
+    "highest_snr": score_weights(gsnr=-1),
+    "lowest_margin": score_weights(margin=1),
+    # fewest slot-hops; among equals the shorter-listed route, then the lower start (both far below one slot-hop: k < 2^7, s < 2^10)
+    "least_slot_hops": score_weights(slot_hops=1, route=2.0 ** -8, start=2.0 ** -20),
+}
+
+
+def score_preset(name: str, n_mods: int, n_slots: int) -> np.ndarray:
+    """A copy of the weight vector SCORE_PRESETS[name] for a configuration with n_mods formats and n_slots slots"""
+    w = SCORE_PRESETS[name]
+    return w(n_mods, n_slots) if callable(w) else w.copy()
 
 _i32p, _f64p = C.POINTER(C.c_int32), C.POINTER(C.c_double)
 
@@ -296,10 +328,22 @@ ABSENT_FROM_OLDER_BUILDS = (
     "ongym_repair_links", "ongym_failed_links", "ongym_move_services", "ongym_spectrum_map", "ongym_admission_map",
     "ongym_playout", "ongym_sample_actions", "ongym_query_link_weight_entry", "ongym_query_path_rows", "ongym_set_stream")
 
+# The prototype of include/ongym_score.h (ongym.h includes it behind its own declarations), held to that header by
+# tests/test_score_host.py.  The in-tree library must export it; an older build named by ONGYM_HIP_LIB may lack it.
+SCORE_SIGNATURES = {
+    "ongym_score_actions": (_i32, (_vp, _vp, _i32, _vp, _vp, _vp)),
+}
+
 _LIB = None
 
 
 def _declare(lib):
+    for name, (restype, argtypes) in SCORE_SIGNATURES.items():
+        if hasattr(lib, name):
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, list(argtypes)
+        elif not os.environ.get("ONGYM_HIP_LIB"):
+            raise RuntimeError(f"{lib._name} does not export {name}")
     for name, (restype, argtypes) in SIGNATURES.items():
         if hasattr(lib, name):
             fn = getattr(lib, name)

@@ -302,6 +302,39 @@ class BatchedQRMSAEnv:
         io.call("ongym_action_impact", A, io.ptr(actions), io.ptr(svc), io.ptr(res))
         return ret
 
+    # ---- weighted candidate scoring, weights per replica (ongym_score_actions, include/ongym_score.h) ----------------------
+    def score_preset(self, name: str) -> np.ndarray:
+        """float64 [10]: the weight vector nat.SCORE_PRESETS[name] for this configuration"""
+        c = self.holder.struct
+        return nat.score_preset(name, c.n_mods, c.n_slots)
+
+    def score_actions(self, weights, out=None, detail=False):
+        """The step action with the lowest w . x among the feasible placements of every replica's pending request: int32 [B].
+        x are the ten features nat.SCORE_FEATURES of a candidate (route, hops, format rank, slots, slot-hops, start, route load,
+        touch, GSNR, margin); the candidates are highest SNR's (every route, every format, every start with spectrum), feasible
+        when they pass QoT with the replica's margin; no feasible candidate: the reject action.  weights: float64 [10] (one
+        vector for every replica) or [B, 10] (a vector per replica: a population of heuristics in one launch);
+        score_preset(name) gives the named ones.  detail=True returns (actions, best, counts): best float64 [B, 11], the
+        winner's score and features (NaN without a winner), counts int32 [B, 3], columns nat.SCORE_COUNT_COLUMNS.  Read-only;
+        `env.step(env.score_actions(W))` is one decision of the population.  A host environment takes and returns numpy arrays
+        and refuses a weight that is not finite.  An io_device environment takes a torch.float64 tensor on its device and
+        writes into `out` (the actions tensor, or with detail the triple (actions, best, counts)), on torch's current stream
+        (env.set_stream), without synchronising; its weights are not inspected."""
+        B, F = self.batch_size, len(nat.SCORE_FEATURES)
+        self._needs_every_format("score_actions walks")
+        io = io_for(self)
+        weights, _ = io.array(weights, "weights", np.float64, [(F,), (B, F)], f"({F},) or ({B}, {F})",
+                              host_too=(lambda w: np.asarray(w, np.float64) if isinstance(w, (list, tuple)) else w,
+                                        " or a list of floats", ""))
+        if isinstance(weights, np.ndarray) and not np.all(np.isfinite(weights)):
+            raise ValueError("weights must be finite")
+        (actions, best, counts), ret = io.outputs(out, [("actions", np.int32, (B,)), ("best", np.float64, (B, 1 + F)),
+                                                        ("counts", np.int32, (B, len(nat.SCORE_COUNT_COLUMNS)))],
+                                                  "an int32 tensor of shape (B,) (detail: with a float64 tensor of shape (B, 11) and "
+                                                  "an int32 tensor of shape (B, 3), as a triple)", detail=bool(detail))
+        io.call("ongym_score_actions", io.ptr(weights), int(weights.ndim == 2), io.ptr(actions), io.ptr(best), io.ptr(counts))
+        return ret
+
     # ---- single-link failures and first-fit restoration (ongym_failure_impact, include/ongym.h) ----------------------------
     def failure_impact(self, links=None, out=None, detail=False):
         """What happens when a fibre is cut: float64 [B, F, 10], columns nat.FAILURE_IMPACT (status, victims, their capacity,

@@ -583,6 +583,23 @@ class QRMSAEnv:
         self._sticky_policy = int(policy)      # the next step() asks the device for this policy's next decision in the same call
         return a0, bool(f0 & nat.F_BLOCKED_RESOURCES), bool(f0 & nat.F_BLOCKED_OSNR)
 
+    def score_action(self, weights) -> dict:
+        """The weighted scoring policy on the current request (BatchedQRMSAEnv.score_actions): weights are ten floats in the
+        order of nat.SCORE_FEATURES, or the name of one of nat.SCORE_PRESETS.  A dict: action, blocked_resources, blocked_osnr
+        (the plugin tuple's three), candidates and feasible (how many placements had spectrum, how many of them passed QoT),
+        score, and the winner's features by name (None without a winner)."""
+        if isinstance(weights, str):
+            weights = self._dev.score_preset(weights)
+        a, best, counts = self._dev.score_actions(np.asarray(weights, np.float64), detail=True)
+        flags, won = int(counts[0, 2]), not np.isnan(best[0, 0])
+        whole = ("route", "hops", "format_rank", "slots", "slot_hops", "start", "touch")
+        out = dict(action=int(a[0]), blocked_resources=bool(flags & nat.F_BLOCKED_RESOURCES),
+                   blocked_osnr=bool(flags & nat.F_BLOCKED_OSNR), candidates=int(counts[0, 0]), feasible=int(counts[0, 1]),
+                   score=float(best[0, 0]) if won else None)
+        for k, v in zip(nat.SCORE_FEATURES, best[0, 1:]):
+            out[k] = None if not won else int(v) if k in whole else float(v)
+        return out
+
     def first_fit_action(self):
         """heuristic_shortest_available_path_first_fit_best_modulation (heuristics.py:923-966) on device."""
         return self.policy_action(nat.POLICY_FIRST_FIT)

@@ -528,3 +528,12 @@ def heuristic_psr(env, variant: str = "O", coef_dist: float = 1.0, coef_slots: f
     if all(_m.isfinite(v) and v > 0 for v in (coef_dist, coef_slots)):
         return get_qrmsa_env(env).policy_action(_nat.POLICY_PSR)
     return heuristic_psr_plugin(env, variant, coef_dist, coef_slots)
+
+
+def heuristic_weighted(env, weights):
+    """The placement with the lowest weights . features among those that pass QoT, scored on device in one launch
+    (ongym_score_actions; QRMSAEnv.score_action has the features and the winner's values).  weights: ten floats in the order of
+    `_native.SCORE_FEATURES`, or the name of one of `_native.SCORE_PRESETS` ("highest_snr" answers as heuristic_highest_snr
+    does).  Returns the plugin tuple (action, blocked_resources, blocked_osnr)."""
+    res = get_qrmsa_env(env).score_action(weights)
+    return res["action"], res["blocked_resources"], res["blocked_osnr"]
